@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: batched receding-horizon MPC solves on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]     (N > 1: starts its N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                            (N > 1: starts its N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,10 +15,14 @@ warm-started from the previous step's shifted solution; the first warmup step
 is cold) + the plant/shift update, all on the device.  Weak scaling: every rank
 owns B instances; no collective inside the timed region.
 
+A plain run sets up, warms up, times the K steps, saves its outputs (--dump-outputs) and
+prints the headline line; every further measurement below is part of --full.
+
 Printed JSON (rank 0): value = total solves/s over all ranks; ms_per_step = the
-max-over-ranks wall time per step; ms_per_solve_p50 = median batched solve-call
-latency (HIP events).  `roofline` describes the kernel that dominates the timed
-region, the fused solve_kernel: algorithmic FP64 flops per launch (the flops one
+max-over-ranks wall time per step.  With --full: ms_per_solve_p50 = median batched solve-call
+latency (HIP events) of K further lock-step launches; `reference_warm_start` = the same
+timings under the reference's warm-start policy.  `roofline` describes the kernel that
+dominates the timed region, the fused solve_kernel: algorithmic FP64 flops per launch (the flops one
 IPM iteration of one instance needs -- per-node evaluation and Riccati step
 measured by tools/flop_probe.py, profiles/r04_flop_probe.json, plus the IPM's
 vector work counted in ipm_vector_flops; DESIGN.md §6 -- x the launch's
@@ -117,6 +122,16 @@ def parse():
                          "lockstep: one launch per step")
     ap.add_argument("--roofline-batch", type=int, default=1 << 19)
     ap.add_argument("--roofline-reps", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the lock-step latency run (lockstep, ms_per_solve_p50, "
+                         "solve_kernel), the reference's warm-start policy, the rooflines and the CPU baseline "
+                         "(each of the --no-* switches below drops its part of --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save what the last timed step left with the caller (w, f, lam_g, "
+                         "lam_x, P, status, iters: one row per instance) and the rows' global instance ids as "
+                         "float64 DIR/<name>.npy (with --gpus N > 1 every rank saves its own DIR/<name>_rank<r>.npy); "
+                         "at most 64 MB per rank: a larger batch is dumped as a fixed sample of instances drawn "
+                         "from --seed")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--dump-stats", default=None,
@@ -204,6 +219,19 @@ def cpu_baseline(make_P, N, steps, cores, min_seconds=10.0, max_reps=64, warm=(1
             lamx0 = shift_lamx_np(r["lam_x"], N)
         reps += 1
     return n / t_solve, t_solve, reps, its / max(n, 1)
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of one rank together
+
+
+def dump_instances(B, per_instance, seed, budget=DUMP_BUDGET_BYTES):
+    """Rows of a (B, ...) float64 dump that keep it within the budget: every instance when
+    B * per_instance doubles (and the .npy headers) fit, else a sorted sample without replacement
+    that depends only on (seed, B, per_instance) -- the same rows in every run and build."""
+    n = (budget - 4096) // (8 * per_instance)
+    if B <= n:
+        return np.arange(B, dtype=np.int64)
+    return np.sort(np.random.default_rng([seed, B]).choice(B, size=int(n), replace=False)).astype(np.int64)
 
 
 def _pseq(refs, n_p, nx):
@@ -505,7 +533,8 @@ def main():
     N = args.N or {2: 20, 3: 30, 4: 50, 5: 100}[cfg]
     B = args.batch or {2: 1024, 3: 4096, 4: 1024, 5: 2048}[cfg]
     start, stop = mdist.shard(B, rank)
-    T_all = args.warmup + 2 * args.steps  # warmup, timed multi-step run, lock-step latency run
+    # warmup, timed multi-step run and (--full) the lock-step latency run
+    T_all = args.warmup + (2 if args.full else 1) * args.steps
     per_step = None  # per-step device updates (stage references / schedules), resident in HBM
     seq = lambda t0, K: (None, None)  # noqa: E731  same, as sequences for a multi-step launch
     if variant is not None:
@@ -572,9 +601,9 @@ def main():
 
     def closed_loop(warm_duals):
         """W untimed warm-up steps, K timed steps (one multi-step launch, or K launches in
-        --mode lockstep), then K lock-step launches timed with HIP events (the latency a real-time
-        loop sees per step), under one warm-start policy (POLICY).  Every policy starts from the
-        same P0 and the same per-step references."""
+        --mode lockstep), then (--full) K lock-step launches timed with HIP events (the latency a
+        real-time loop sees per step), under one warm-start policy (POLICY).  Every policy starts
+        from the same P0 and the same per-step references."""
         loop = DeviceLoop(solver, P0, device=dev, stream=stream, warm_duals=warm_duals)
         warm_it = torch.zeros((max(args.warmup, 1), B), dtype=torch.int32, device=loop.P.device)
         for t in range(args.warmup):
@@ -614,6 +643,24 @@ def main():
         if world > 1:
             torch.distributed.barrier()
         elapsed = mdist.max_over_ranks(t1 - t0, device=loop.P.device)
+        dv = loop.P.device
+        res = {"loop": loop, "warm_it": warm_it, "iters_hist": iters_hist, "status_hist": status_hist,
+               "elapsed": elapsed,
+               "iters_max_step": mdist.max_over_ranks(float(iters_hist.max(dim=1).values.double().mean().item()),
+                                                      device=dv),
+               "iters_mean": mdist.max_over_ranks(float(iters_hist.double().mean().item()), device=dv),
+               "run_ms": ev_run[0].elapsed_time(ev_run[1]) if args.mode == "async" else None}
+        if args.dump_outputs and warm_duals:
+            # what the last timed step left with a caller of the timed path (DeviceLoop.run / step);
+            # copied here because the loop's tensors are overwritten by the lock-step run of --full
+            outs = {"w": loop.w, "f": loop.f, "lam_g": loop.lam, "lam_x": loop.lamx, "P": loop.P,
+                    "status": status_hist[K - 1], "iters": iters_hist[K - 1]}
+            sel = dump_instances(B, sum(v[0].numel() for v in outs.values()) + 1, args.seed)
+            idx = torch.from_numpy(sel).to(dv)
+            res["outputs"] = {k: v.index_select(0, idx).double().cpu().numpy() for k, v in outs.items()}
+            res["outputs"]["instance"] = (start + sel).astype(np.float64)  # global instance ids of the rows
+        if not args.full:
+            return res
 
         # lock-step latency: K further steps, one launch each, HIP events on the launch stream
         # (ms_per_solve_p50 = the latency a real-time loop sees per closed-loop step)
@@ -632,21 +679,22 @@ def main():
         tl1 = time.perf_counter()
         lock_elapsed = mdist.max_over_ranks(tl1 - tl0, device=loop.P.device)
         solve_ms = sorted(a.elapsed_time(b) for a, b in ev)
-        dv = loop.P.device
-        return {"loop": loop, "warm_it": warm_it, "iters_hist": iters_hist, "status_hist": status_hist,
-                "lk_st": lk_st, "lk_it": lk_it, "elapsed": elapsed, "lock_elapsed": lock_elapsed,
-                "solve_ms": solve_ms, "p50": mdist.max_over_ranks(float(np.median(solve_ms)), device=dv),
-                "lock_iters_max": mdist.max_over_ranks(float(lk_it.max(dim=1).values.double().mean().item()), device=dv),
-                "iters_max_step": mdist.max_over_ranks(float(iters_hist.max(dim=1).values.double().mean().item()),
-                                                       device=dv),
-                "iters_mean": mdist.max_over_ranks(float(iters_hist.double().mean().item()), device=dv),
-                "run_ms": ev_run[0].elapsed_time(ev_run[1]) if args.mode == "async" else float(np.sum(solve_ms))}
+        res.update({"lk_st": lk_st, "lk_it": lk_it, "lock_elapsed": lock_elapsed, "solve_ms": solve_ms,
+                    "p50": mdist.max_over_ranks(float(np.median(solve_ms)), device=dv),
+                    "lock_iters_max": mdist.max_over_ranks(float(lk_it.max(dim=1).values.double().mean().item()),
+                                                           device=dv)})
+        if args.mode != "async":
+            res["run_ms"] = float(np.sum(solve_ms))
+        return res
 
     res = closed_loop(warm_duals=True)  # the headline policy ("dual")
-    ref_res = closed_loop(warm_duals=False) if not args.no_reference_warm_start else None
+    ref_res = closed_loop(warm_duals=False) if args.full and not args.no_reference_warm_start else None
     loop, warm_it, iters_hist, status_hist = res["loop"], res["warm_it"], res["iters_hist"], res["status_hist"]
-    lk_it, elapsed, lock_elapsed, solve_ms = res["lk_it"], res["elapsed"], res["lock_elapsed"], res["solve_ms"]
-    p50, lock_iters_max = res["p50"], res["lock_iters_max"]
+    elapsed = res["elapsed"]
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in res["outputs"].items():  # one file per rank and array (rank 0 of a world of 1: <name>.npy)
+            np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
     # closed-loop statistics: the only collective (RCCL all_gather over xGMI), outside the timed region
     def P_fin_of(lp):
@@ -672,7 +720,34 @@ def main():
     # group-iterations of every solve launch of this run, both policies (PMC normalisation,
     # tools/solve_pmc_summary.py)
     iters_all = sum(int(r["warm_it"][:args.warmup].sum().item() + r["iters_hist"].sum().item() +
-                        r["lk_it"].sum().item()) for r in (res, ref_res) if r is not None)
+                        (r["lk_it"].sum().item() if args.full else 0)) for r in (res, ref_res) if r is not None)
+
+    # the headline line; everything below it belongs to --full
+    out = {
+        "metric": METRIC, "value": round(world * B * K / elapsed, 1), "unit": "solves/s", "n_gpus": world,
+        "steps": K, "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 4),
+        "mode": args.mode, "full": args.full, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64",
+        "data": DATA_V[variant] if variant else DATA[cfg],
+        "config": {"workload": (workload_name_v(variant, N, ocp.M) if variant else workload_name(cfg, N)) +
+                               "; " + POLICY["dual"],
+                   "warm_start_policy": "dual",
+                   "dynamics": DYN_V[variant] if variant else DYN[cfg], "N": N,
+                   "M": getattr(ocp, "M", None), "batch_per_gpu": B, "global_batch": B * world,
+                   "parallelism": f"instance-sharded x{world} (no data-path collective)"},
+        "iters_mean": round(float(S_all[:, 1].mean()), 2), "iters_max": int(S_all[:, 2].max()),
+        "iters_max_per_step_mean": round(float(iters_max_step), 2),
+        "failed_instances": int((S_all[:, 3] > 1).sum()),
+        "iters_sum_all_steps": int(iters_all),
+        "mpcx_source_hash": _lib.source_hash(),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    lk_it, lock_elapsed, p50, lock_iters_max = res["lk_it"], res["lock_elapsed"], res["p50"], res["lock_iters_max"]
 
     roof = None
     if rank == 0 and not args.no_roofline and cfg == 2:
@@ -762,31 +837,14 @@ def main():
             "us_per_ipm_iteration": round(r_["p50"] * 1e3 / max(r_["lock_iters_max"], 1.0), 2),
             "timed_launch_ms": round(r_["run_ms"], 4)}
     if rank == 0:
-        total = world * B * K
-        out = {
-            "metric": METRIC, "value": round(total / elapsed, 1), "unit": "solves/s", "n_gpus": world,
-            "steps": K, "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 4),
-            "mode": args.mode,
+        out.update({
             "lockstep": {"value": round(world * B * K / lock_elapsed, 1),
                          "ms_per_step": round(lock_elapsed / K * 1e3, 4),
                          "iters_max_per_step_mean": round(float(lock_iters_max), 2)},
-            "ms_per_solve_p50": round(p50, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64",
-            "data": DATA_V[variant] if variant else DATA[cfg],
-            "config": {"workload": (workload_name_v(variant, N, ocp.M) if variant else workload_name(cfg, N)) +
-                                   "; " + POLICY["dual"],
-                       "warm_start_policy": "dual",
-                       "dynamics": DYN_V[variant] if variant else DYN[cfg], "N": N,
-                       "M": getattr(ocp, "M", None), "batch_per_gpu": B, "global_batch": B * world,
-                       "parallelism": f"instance-sharded x{world} (no data-path collective)"},
-            "iters_mean": round(float(S_all[:, 1].mean()), 2), "iters_max": int(S_all[:, 2].max()),
-            "iters_max_per_step_mean": round(float(iters_max_step), 2),
-            "failed_instances": int((S_all[:, 3] > 1).sum()),
-            "iters_sum_all_steps": int(iters_all),
+            "ms_per_solve_p50": round(p50, 4),
             "reference_warm_start": ref_block,
             "roofline": roof_solve, "roofline_sweep": roof, "cpu_baseline": cpu, "solve_kernel": solve_info,
-            "mpcx_source_hash": _lib.source_hash(),
-        }
+        })
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

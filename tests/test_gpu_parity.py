@@ -1044,6 +1044,75 @@ def test_bench_two_ranks_rehearsal(tmp_path, workload, B):
         np.testing.assert_array_equal(stats[name], stats["single"], err_msg=name)
 
 
+@pytest.mark.parametrize("B,K,W,sampled", [
+    (192, 3, 2, False),    # three 64-lane waves' worth of instances, not the default batch: every row is dumped
+    (32768, 2, 1, True),   # 279 doubles per instance: all rows would be 73 MB, so a seeded sample is dumped
+], ids=["all_rows", "over_budget_sample"])
+def test_bench_plain_line_and_dump_outputs(tmp_path, mpcx, B, K, W, sampled):
+    """A plain bench run prints the headline line only (no --full measurement in it) and
+    --dump-outputs saves what its timed path left with the caller: bit for bit the rows of the
+    tensors of a DeviceLoop driven here through the same W warm-up steps and one K-step launch (the
+    expected numbers come from the same library path: this checks the bench's inputs, sequencing,
+    file names and dtypes), float64 .npy of at most 64 MB together; for a batch over the budget a
+    sample of instances, and the same files, rows and bits from a second run with the same arguments
+    (for the small batch the in-process comparison already pins every bit)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import torch
+    from conftest import ROOT
+    from mpcx import dist
+    from mpcx.device import DeviceLoop
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+           "--batch", str(B), "--dump-outputs"]
+    out = subprocess.run(cmd + [str(tmp_path / "dump")], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["warmup"] == W and d["full"] is False and d["failed_instances"] == 0
+    assert d["unit"] == "solves/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["ms_per_step"] > 0 and math.isclose(d["value"], B * 1e3 / d["ms_per_step"], rel_tol=1e-2)
+    for k in ("lockstep", "ms_per_solve_p50", "reference_warm_start", "roofline", "roofline_sweep", "cpu_baseline",
+              "solve_kernel"):
+        assert k not in d
+
+    ipopt = {"max_iter": 2000, "acceptable_tol": 1e-8, "acceptable_obj_change_tol": 1e-6}
+    solver = mpcx.nlpsol("s", "mi355x", mpcx.unicycle_point_to_point(N=20), {"ipopt": ipopt}, device=0)
+    loop = DeviceLoop(solver, dist.config2_inputs(0, B), device="cuda:0")
+    for _ in range(W):
+        loop.step()
+    st, it = loop.run(K)
+    torch.cuda.synchronize()
+    want = {"w": loop.w, "f": loop.f, "lam_g": loop.lam, "lam_x": loop.lamx, "P": loop.P, "status": st[K - 1],
+            "iters": it[K - 1]}
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == sorted(k + ".npy" for k in list(want) + ["instance"])
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in files) <= 64 * 10 ** 6
+    inst = np.load(tmp_path / "dump" / "instance.npy")
+    sel = inst.astype(np.int64)
+    assert inst.dtype == np.float64 and np.all(np.diff(sel) > 0) and sel[0] >= 0 and sel[-1] < B
+    if sampled:  # as many rows as the budget holds (within one row and the files' headers), not a prefix
+        per = 8 * (sum(int(np.prod(t.shape[1:])) for t in want.values()) + 1)
+        assert (64 * 10 ** 6 - 8192) // per - 1 <= len(sel) < B and sel[-1] >= B - B // 64
+    else:
+        assert np.array_equal(sel, np.arange(B))
+    for k, t in want.items():
+        a = np.load(tmp_path / "dump" / (k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (len(sel),) + tuple(t.shape[1:]), k
+        np.testing.assert_array_equal(a, t.double().cpu().numpy()[sel], err_msg=k)
+    if sampled:  # a second run with the same arguments: the same files, the same rows, the same bits
+        again = subprocess.run(cmd + [str(tmp_path / "dump2")], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert again.returncode == 0, again.stderr[-3000:]
+        assert sorted(os.listdir(tmp_path / "dump2")) == files
+        for f in files:
+            np.testing.assert_array_equal(np.load(tmp_path / "dump" / f), np.load(tmp_path / "dump2" / f), err_msg=f)
+    assert np.all(want["status"].cpu().numpy() <= 1) and np.abs(np.load(tmp_path / "dump" / "w.npy")).max() > 1.0
+
+
 def test_mpctools_variant_closed_loop_3exemplo(mpcx, R, golden):
     """mpctools/multiple_shooting_mpctools.py on the GPU (node cost, RK4 M=1, R = I): each
     solve starts from the previous prediction X_1, the plant is the exact ODE flow; the

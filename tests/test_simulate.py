@@ -1,26 +1,31 @@
-"""The reference's own visualisation, ``simulation_code.simulate`` (/root/reference/simulation_code.py:10-94),
-driven UNCHANGED on the closed-loop arrays mpcx produces ("the driver loop ...
-plus simulation_code.simulate, must run unchanged on these outputs").
+"""The closed-loop arrays mpcx records are the ones the reference's visualisation animates
+("the driver loop ... plus simulation_code.simulate, must run unchanged on these
+outputs").
 
-The arrays come from mpcx/record.py's ClosedLoopLog -- the class the GPU closed-loop test
+tests/golden/simulate_frames.npz holds what the reference's ``simulate(cat_states, cat_controls, t,
+step_horizon, N, reference)`` drew, frame by frame, when it ran unchanged on the arrays of
+``reference_loop_log`` below (recorded by tests/golden/make_simulate_frames.py: the data of the path
+line, the horizon line and the pose polygons after every frame, the axes' limits, and the shapes
+of the arrays it accepted; the script itself is not part of this repository).  The arrays come from
+mpcx/record.py's ClosedLoopLog -- the class the GPU closed-loop test
 (tests/test_gpu_parity.py::test_casadi_call_shapes_and_closed_loop) fills from mpcx.nlpsol --
 here filled by the reference's driver loop (Casadi/multiple_shooting_casadi.py:224-298, its
 stacked-layout warm start included) run on the C++ CPU oracle, which reproduces 1exemplo.xlsx.
-CPU only; it reads /root/reference, so it runs in the build container and is skipped where the
-reference is absent (the GPU box).  matplotlib runs on the Agg backend and FuncAnimation is
-replaced by a driver that calls the script's init_func and animate(i) for every frame and renders
-the figure after each, so every frame the animation would show is drawn.
+The test rebuilds the log and holds it to the recording: same shapes and dtypes as the arrays the
+script accepted, one frame per entry of ``t``, and every drawn path point and horizon node equal to
+the log's entry.  CPU only.
+
+Tolerance: the recording and the rebuilt log are the same oracle loop, each solve converged to
+IPOPT's tol 1e-8, possibly on another CPU or compiler; 1e-6 absolute is the bound that pins this
+loop to the reference's exported rows below, on states of magnitude up to 10.
 """
-import importlib.util
 import math
 import os
 
 import numpy as np
-import pytest
 
-REF_SIM = "/root/reference/simulation_code.py"
-
-pytestmark = pytest.mark.skipif(not os.path.exists(REF_SIM), reason="reference sources absent (GPU box)")
+FRAMES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "simulate_frames.npz")
+TOL = 1e-6
 
 
 def reference_loop_log(N=10, T=0.2):
@@ -52,41 +57,34 @@ def reference_loop_log(N=10, T=0.2):
     return log, mpc_iter
 
 
-def test_reference_simulate_runs_unchanged_on_closed_loop_log(monkeypatch, golden):
-    matplotlib = pytest.importorskip("matplotlib")
-    matplotlib.use("Agg", force=True)
-    from matplotlib import animation
-
-    drawn = []
-
-    class EveryFrame:
-        """FuncAnimation stand-in: init, then animate(i) and a full render for each frame."""
-
-        def __init__(self, fig=None, func=None, frames=None, init_func=None, **kw):
-            if init_func is not None:
-                init_func()
-            n = frames if isinstance(frames, int) else len(list(frames))
-            for i in range(n):
-                func(i)
-                fig.canvas.draw()
-                drawn.append(i)
-
-        def save(self, *a, **kw):
-            raise AssertionError("simulate(save=False) must not save")
-
-    monkeypatch.setattr(animation, "FuncAnimation", EveryFrame)
-    spec = importlib.util.spec_from_file_location("simulation_code", REF_SIM)
-    sim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(sim)  # module body: imports and the function definition only
-
+def test_closed_loop_log_reproduces_recorded_simulate_frames(golden):
     N, T = 10, 0.2
     log, iters = reference_loop_log(N, T)
     rows = np.array(golden["multiple_shooting"]["rows"])
+    rec = np.load(FRAMES)
     assert iters == 84 and log.cat_states.shape == (3, N + 1, 85)
     # the arrays are the reference's (cat_states[:, 0, :] = its exported state rows)
-    assert np.max(np.abs(log.cat_states[:, 0, :].T - rows[:, 0:3])) < 1e-6
-    reference = np.array([0.0, 0.0, 0.0, 10.0, 10.0, 0.0])  # [x_init, y_init, theta_init, x_target, ...]
-    # the script's own (commented) call, :312-313: simulate(cat_states, cat_controls, times, T, N, ...)
-    sim.simulate(log.cat_states, log.cat_controls, log.times, T, N, reference, save=False)
-    assert drawn == list(range(len(log.t))) and len(log.t) == 85
+    assert np.max(np.abs(log.cat_states[:, 0, :].T - rows[:, 0:3])) < TOL
+    # the call the recording made is the script's own (commented) one, :312-313:
+    # simulate(cat_states, cat_controls, times, T, N, reference), on arrays shaped and typed like the log's
+    assert int(rec["N"]) == N and float(rec["step_horizon"]) == T
+    for a, shape in ((log.cat_states, rec["shape_cat_states"]), (log.cat_controls, rec["shape_cat_controls"]),
+                     (log.times, rec["shape_t"]), (log.t, rec["shape_t"])):
+        assert a.dtype == np.float64 and a.shape == tuple(shape)
+    n = int(rec["frames"])
+    assert n == len(log.times) == len(log.t) == 85  # one frame per record
+    assert rec["horizon"].shape == (n, 2, N + 1) and rec["path_x"].shape == rec["path_y"].shape == (n, n)
+    # every frame's horizon line is that record's predicted (x, y) trajectory ...
+    assert np.max(np.abs(rec["horizon"] - log.cat_states[0:2].transpose(2, 0, 1))) < TOL
+    # ... and its path line the first predicted node of every record so far (nothing drawn beyond)
+    first = log.cat_states[0:2, 0, :]
+    for c, drawn in enumerate((rec["path_x"], rec["path_y"])):
+        want = np.where(np.tri(n, dtype=bool), first[c][None, :], np.nan)
+        assert np.array_equal(np.isnan(drawn), np.isnan(want))
+        assert np.nanmax(np.abs(drawn - want)) < TOL
+    # what it drew stays inside the axes it set from `reference`; the vehicle polygon moves with the pose
+    lo, hi = float(rec["xlim"][0]), float(rec["xlim"][1])
+    assert tuple(rec["ylim"]) == (lo, hi) and lo <= rec["horizon"].min() and rec["horizon"].max() <= hi
+    assert np.array_equal(rec["reference"], [0.0, 0.0, 0.0, 10.0, 10.0, 0.0])
+    assert rec["vehicle"].shape == (n, 4, 2) and np.all(np.isfinite(rec["vehicle"]))
     assert math.isclose(float(log.t[-1, 0]), 83 * T)

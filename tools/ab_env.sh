@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of a run-time knob on one box, alternating runs of the same tree: tools/ab_env.sh "bench args" reps "VAR=value"
 set -uo pipefail
-ARGS=$1; R=${2:-2}; KNOB=$3
+ARGS="--full $1"; R=${2:-2}; KNOB=$3
 mkdir -p gpurun_out/ab
 for i in $(seq 1 "$R"); do
   for n in default knob; do

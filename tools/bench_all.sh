@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/bench_all
 mkdir -p "$O"
 cd "$R"
-run() { local name=$1; shift; timeout -k 10 300 python -u bench.py --no-cpu --no-roofline "$@" > "$O/$name.log" 2>&1; grep '^{' "$O/$name.log" | tail -1 > "$O/$name.json"; }
+run() { local name=$1; shift; timeout -k 10 300 python -u bench.py --full --no-cpu --no-roofline "$@" > "$O/$name.log" 2>&1; grep '^{' "$O/$name.log" | tail -1 > "$O/$name.json"; }
 run c2 --config 2
 run c3 --config 3
 run c4 --config 4

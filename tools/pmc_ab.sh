@@ -11,6 +11,6 @@ for L in "$@"; do
   O=$R/gpurun_out/pmc_ab/$n
   mkdir -p "$O"
   MPCX_LIB=$R/$L MPCX_ALLOW_STALE_LIB=1 timeout -s KILL 120 rocprofv3 --pmc $CNT --output-format csv -d "$O" -o pmc -- \
-    python3 "$R/bench.py" $ARGS --mode lockstep --no-cpu --no-roofline > "$O/run.log" 2>&1 || { echo "pmc failed for $n"; exit 1; }
+    python3 "$R/bench.py" --full $ARGS --mode lockstep --no-cpu --no-roofline > "$O/run.log" 2>&1 || { echo "pmc failed for $n"; exit 1; }
   python3 "$R/tools/pmc_table.py" "$O" solve_kernel
 done

@@ -35,10 +35,10 @@ for STEP in "$@"; do
         --timeout-method thread > "$OUT/gputest_all.log" 2>&1) || { grep -E "FAILED|passed|failed" "$OUT/gputest_all.log" | tail; exit 1; }
       tail -1 "$OUT/gputest_all.log" ;;
     bench)
-      (cd "$R" && timeout -k 10 400 python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err")
+      (cd "$R" && timeout -k 10 400 python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err")
       tail -c 400 "$OUT/bench_default.json"
       (cd /tmp && TMPDIR=/tmp timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/prof_bench" -o bench -- python3 "$R/bench.py" --no-cpu > "$OUT/bench_prof.log" 2>&1) ;;
+        -d "$OUT/prof_bench" -o bench -- python3 "$R/bench.py" --full --no-cpu > "$OUT/bench_prof.log" 2>&1) ;;
     benchall)
       bash "$R/tools/bench_all.sh" ;;
     pmc)

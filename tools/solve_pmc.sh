@@ -10,7 +10,7 @@ OUT=${SOLVE_PMC_OUT:-$R/gpurun_out/solve_pmc}
 mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
-ARGS=(--mode lockstep --steps 5 --warmup 2 --no-cpu --no-roofline ${SOLVE_PMC_ARGS:-})
+ARGS=(--full --mode lockstep --steps 5 --warmup 2 --no-cpu --no-roofline ${SOLVE_PMC_ARGS:-})
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU \
   SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d "$OUT/a" -o pmc -- python3 "$R/bench.py" "${ARGS[@]}" \
   > "$OUT/a.log" 2>&1
