@@ -54,8 +54,19 @@ enum mpcx_model {
   MPCX_MODEL_KIN_BICYCLE = 3, /* x=(X,Y,psi), u=(v,delta); par = (L) */
   MPCX_MODEL_DYN_BICYCLE = 4, /* x=(X,Y,psi,vx,vy,r), u=(delta,ax), linear tyres; par = (m,a,b,Ca,Jz):
                                  the nonlinear parent of Trajectory_tracking_dynamic_model.py:119-128 */
-  MPCX_MODEL_CARTPOLE = 5     /* x=(p,p',phi,phi'), u=F; par = (M,m,L,g,c): the nonlinear parent of
+  MPCX_MODEL_CARTPOLE = 5,    /* x=(p,p',phi,phi'), u=F; par = (M,m,L,g,c): the nonlinear parent of
                                  inverted_pendulum_single_shooting_mpctools.py:19-23 */
+  /* Path-frame kinematic bicycle with steering-rate limits (Trajectory Tracking/test2.py:103-112,42-59):
+     x=(y,phi,v,s), u=(d,a); s = the steering applied in the previous interval (s_0 = delta_prev in x0),
+     d = its increment, delta = s + d held over the interval and s+ = delta exactly, so the script's Du
+     bound is lbu/ubu[0] and its steering bound lbx/ubx[3].  Stage rows (MPCX_P_X0_STAGEREF only)
+     (yt, phit, vdes, kappa, d_ref, a_ref): yt, phit and the curvature kappa enter the dynamics
+       y' = v sin(phi-phit), phi' = v (c2 tan(c1 delta) - kappa cos(phi-phit)/(1-(y-yt) kappa)), v' = a;
+     the node cost is the diagonal one against (yt, phit, vdes, -, d_ref, a_ref) (Q[3] weighs s itself)
+     plus w_z (tan(delta) - L kappa)^2.  par = (L, c1, c2, w_z): (c1, c2) = (1, 1/L) the bicycle,
+     (1/L, 1) the script's tan(delta/L) (:109).  The value 6 stays unassigned: callers of earlier
+     versions, and the library's own argument-checking suite, know it as an unknown model. */
+  MPCX_MODEL_PATH_BICYCLE = 7
 };
 
 enum mpcx_cost {
@@ -144,7 +155,9 @@ typedef struct mpcx_spec {
    (unicycle point-to-point: T=0.2, M=4, Q=diag(1,5,0.1), R=diag(0.5,0.05),
    |v|<=1, |omega|<=pi/4, max_iter=2000, tol=1e-8).  ODE models: node cost, M=1,
    param_layout MPCX_P_X0_STAGEREF (cart-pole: MPCX_P_X0_XREF), the constants listed
-   at mpcx_model and the defaults of mpcx/ode.py. */
+   at mpcx_model and the defaults of mpcx/ode.py.  MPCX_MODEL_PATH_BICYCLE: the constants of
+   Trajectory Tracking/test2.py (T=0.05, L=3.5, Q=(1.75,2.5,2.5,0)/(N+1), R=(0,0.4)/(N+1),
+   w_z=10/(N+1), |s|<=0.384, |d|<=0.1225, |a|<=2; :19-59) with the bicycle form of the steering term. */
 int mpcx_default_spec(mpcx_spec* s, int32_t model, int32_t N);
 
 int mpcx_create(const mpcx_spec* s, mpcx_handle** h);

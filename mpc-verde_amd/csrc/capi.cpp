@@ -92,18 +92,21 @@ int nx_of(const mpcx_spec& s) {
   switch (s.model) {
     case MPCX_MODEL_UNICYCLE: case MPCX_MODEL_KIN_BICYCLE: return 3;
     case MPCX_MODEL_DYN_BICYCLE: return 6;
-    case MPCX_MODEL_CARTPOLE: return 4;
+    case MPCX_MODEL_CARTPOLE: case MPCX_MODEL_PATH_BICYCLE: return 4;
     default: return s.nx;
   }
 }
 int nu_of(const mpcx_spec& s) {
   switch (s.model) {
-    case MPCX_MODEL_UNICYCLE: case MPCX_MODEL_KIN_BICYCLE: case MPCX_MODEL_DYN_BICYCLE: return 2;
+    case MPCX_MODEL_UNICYCLE: case MPCX_MODEL_KIN_BICYCLE: case MPCX_MODEL_DYN_BICYCLE:
+    case MPCX_MODEL_PATH_BICYCLE: return 2;
     case MPCX_MODEL_CARTPOLE: return 1;
     default: return s.nu;
   }
 }
-bool is_ode(int model) { return model >= MPCX_MODEL_KIN_BICYCLE && model <= MPCX_MODEL_CARTPOLE; }
+bool is_ode(int model) {
+  return (model >= MPCX_MODEL_KIN_BICYCLE && model <= MPCX_MODEL_CARTPOLE) || model == MPCX_MODEL_PATH_BICYCLE;
+}
 
 mpcx::OdeParams ode_params(const mpcx_spec& s) {
   mpcx::OdeParams op{};
@@ -284,11 +287,13 @@ int mpcx_default_spec(mpcx_spec* s, int32_t model, int32_t N) {
   s->acceptable_compl_inf_tol = 1e-2;
   s->acceptable_obj_change_tol = 1e-6;
   s->acceptable_iter = 15;
-  if (is_ode(model)) {  // no reference script: IPOPT's defaults
+  // no reference script passes these options (the BASELINE variants have none; test2.py calls
+  // mpctools without IPOPT options): IPOPT's defaults
+  if (is_ode(model)) {
     s->acceptable_tol = 1e-6;
     s->acceptable_obj_change_tol = 1e20;
   }
-  if (is_ode(model)) {  // defaults of the BASELINE config variants (mpcx/ode.py documents them)
+  if (is_ode(model)) {  // common to the ODE models (mpcx/ode.py documents each model's defaults below)
     s->cost = MPCX_COST_NODE;
     s->param_layout = MPCX_P_X0_STAGEREF;
     s->M = 1;
@@ -324,6 +329,16 @@ int mpcx_default_spec(mpcx_spec* s, int32_t model, int32_t N) {
     s->lbu[0] = -200.0; s->ubu[0] = 200.0;  // :28
     const double par[5] = {1.0, 1.0, 0.5, 9.81, 10.0};
     for (int i = 0; i < 5; ++i) s->par[i] = par[i];
+  } else if (model == MPCX_MODEL_PATH_BICYCLE) {  // Trajectory Tracking/test2.py:19-59,118
+    const double n1 = N + 1, L = 3.5;
+    s->T = 0.05;
+    s->Q[0] = 1.75 / n1; s->Q[1] = 2.5 / n1; s->Q[2] = 2.5 / n1;  // lambda1..3 (:42-47); s unweighted
+    s->R[1] = 0.4 / n1;                                          // lambda4 on a - a_ref
+    s->lbu[0] = -0.1225; s->ubu[0] = 0.1225;                     // Du bound (:35-36)
+    s->lbu[1] = -2.0; s->ubu[1] = 2.0;
+    s->lbx[3] = -0.384; s->ubx[3] = 0.384;                       // steering bound, on the carried state
+    s->par[0] = L; s->par[1] = 1.0; s->par[2] = 1.0 / L;         // bicycle form: tan(delta) / L
+    s->par[3] = 10.0 / n1;                                       // lambda5 on (tan(delta) - L kappa)^2
   }
   return 0;
 }
@@ -363,6 +378,13 @@ int mpcx_create(const mpcx_spec* s, mpcx_handle** out) {
     if (!(s->lbx[i] < s->ubx[i])) return fail(MPCX_EINVAL, "lbx must be < ubx");
   if (s->model == MPCX_MODEL_LINEAR && s->param_layout != MPCX_P_X0_STAGEREF)
     return fail(MPCX_EINVAL, "linear model uses param_layout MPCX_P_X0_STAGEREF");
+  if (s->model == MPCX_MODEL_PATH_BICYCLE) {
+    if (s->param_layout != MPCX_P_X0_STAGEREF)
+      return fail(MPCX_EINVAL, "path bicycle uses param_layout MPCX_P_X0_STAGEREF (the stage rows enter the dynamics)");
+    for (int i = 0; i < 4; ++i)
+      if (!std::isfinite(s->par[i])) return fail(MPCX_EINVAL, "path bicycle: par = (L, c1, c2, w_z) must be finite");
+    if (!(s->par[0] > 0)) return fail(MPCX_EINVAL, "path bicycle: L = par[0] must be > 0");
+  }
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev == 0) return fail(MPCX_EHIP, "no HIP device available");

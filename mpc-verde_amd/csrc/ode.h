@@ -15,6 +15,11 @@
 //   CartPole     x = (p, p', phi, phi'), u = F; M, m, L, g, friction c.  Its linearisation at
 //                phi = 0 is exactly the reference's Ac, Bc with M = m = 1, L = 0.5, c = 10
 //                (Inverted_pendulum/inverted_pendulum_single_shooting_mpctools.py:19-23).
+//   PathBicycle  x = (y, phi, v, s), u = (d, a): the path-frame kinematic bicycle of the lane-keeping
+//                study (Trajectory Tracking/test2.py:103-112) with the steering rate limit as a
+//                control box.  Its dynamics read the stage's path row (kStagePar), its cost has a
+//                term outside the diagonal quadratic (kCostHook), and s is a carried state
+//                (kCarried): s+ = s + d exactly, the applied steering s + d held over the interval.
 //
 // Derivatives.  The 6-state bicycle: forward sensitivities and stage adjoints through RK4 with
 // closed-form partials of f (OdeModel::derivs_adjoint, below).  The others, and the 6-state
@@ -359,10 +364,105 @@ struct CartPole {
   }
 };
 
-// RK4, M substeps, one f call site (the four stages are a runtime loop)
+// The path-frame kinematic bicycle with a steering-rate input (Trajectory Tracking/test2.py).
+// States y (lateral position), phi (heading), v (speed) and the carried state s = the steering
+// applied in the previous interval; inputs d (steering increment) and a (acceleration).  The
+// interval's steering delta = s + d is held over all M substeps, and s+ = delta exactly, so the
+// script's |Du| bound (:35-36, 55-59) is the box on d and its steering bound the box on s.
+// Stage row zr = (yt, phit, vdes, kappa, d_ref, a_ref): yt, phit and the path curvature kappa
+// enter f (:103-112),
+//   y'   = v sin(phi - phit)
+//   phi' = v (c2 tan(c1 delta) - kappa cos(phi - phit) / (1 - (y - yt) kappa))
+//   v'   = a,
+// par = (L, c1, c2, w_z): (c1, c2) = (1, 1/L) is the bicycle, (1/L, 1) the script's tan(delta/L)
+// (:109).  Stage cost (:42-49): the diagonal node cost against (yt, phit, vdes, -, d_ref, a_ref)
+// -- slot 3 holds kappa, s has no reference -- plus w_z (tan(delta) - L kappa)^2.
+struct PathBicycle {
+  static constexpr int NX = 4, NU = 2;
+  static constexpr bool kSOC = false;
+  static constexpr unsigned NLMASK = 0x3f;  // y, phi, v, and s, d through delta; a drives v
+  static constexpr unsigned INDEP = 0;
+  // sincos(phi - phit), 1/(1 - (y - yt) kappa); tan(c1 delta) of the held steering
+  static constexpr int kTrigPerEval = 3, kTrigInput = 1, kTrigMaxM = 1;
+  static constexpr bool kAdjoint = false;
+  static constexpr bool kStagePar = true;  // f reads the stage row
+  static constexpr bool kCostHook = true;  // cost_ref / cost_extra / cost_extra_derivs
+  static constexpr int kCarried = 1;       // the last state is carried, not integrated
+  template <class S, class Tc>
+  __device__ __forceinline__ static void f(const S* x, const S* u, const double* par, const double* zr, S* dx, Tc& tc) {
+    const double c1 = par[1], c2 = par[2], yt = zr[0], phit = zr[1], kap = zr[3];
+    S se, ce;
+    tc.sincos_x(x[1] - phit, se, ce);
+    const S iden = tc.recip_x(1.0 - (x[0] - yt) * kap);
+    dx[0] = x[2] * se;
+    dx[1] = x[2] * (c2 * tc.tan_u(c1 * u[0]) - kap * (ce * iden));
+    dx[2] = u[1];
+  }
+  // the inputs f sees: the held steering s + d, and a
+  template <class S>
+  __device__ __forceinline__ static void eff_input(const S* z, S* ue) {
+    ue[0] = z[3] + z[4];
+    ue[1] = z[5];
+  }
+  // the carried state's transition: s+ = s + d
+  template <class S>
+  __device__ __forceinline__ static void carry(const S* ue, S* xf) { xf[3] = ue[0]; }
+  // reference of the diagonal cost: slot 3 of the row is the curvature, not a reference for s
+  __device__ __forceinline__ static double cost_ref(const double* zr, int i) { return i == 3 ? 0.0 : zr[i]; }
+  // w_z (tan(s + d) - L kappa)^2 and its exact derivatives (tan' = 1 + tan^2, tan'' = 2 tan tan')
+  __device__ __forceinline__ static double cost_extra(const double* par, const double* zr, const double* z) {
+    const double r = ::tan(z[3] + z[4]) - par[0] * zr[3];
+    return par[3] * r * r;
+  }
+  __device__ __forceinline__ static void cost_extra_derivs(const double* par, const double* zr, const double* z, double fs,
+                                                           double* g, double* H) {
+    const double t = ::tan(z[3] + z[4]), t1 = fma(t, t, 1.0), r = t - par[0] * zr[3];
+    const double w2 = 2.0 * fs * par[3];
+    const double g1 = w2 * r * t1, h1 = w2 * t1 * fma(2.0 * t, r, t1);  // d/ddelta, d2/ddelta2
+    g[3] += g1;
+    g[4] += g1;
+    H[symix(3, 3, NX + NU)] += h1;
+    H[symix(3, 4, NX + NU)] += h1;
+    H[symix(4, 4, NX + NU)] += h1;
+  }
+};
+
+// What a model may declare beyond f (absent = off; the code below is then what it was without them):
+//   kStagePar  f takes the stage row (Ctx::zr) after par
+//   kCostHook  cost_ref (the diagonal cost's reference), cost_extra and cost_extra_derivs
+//   kCarried   the last kCarried states are not integrated: f sees eff_input(z) and NX - kCarried
+//              states, carry() sets the carried states of xf
+template <class D, class = void>
+struct StageParOf {
+  static constexpr bool value = false;
+};
+template <class D>
+struct StageParOf<D, std::void_t<decltype(D::kStagePar)>> {
+  static constexpr bool value = D::kStagePar;
+};
+template <class D, class = void>
+struct CostHookOf {
+  static constexpr bool value = false;
+};
+template <class D>
+struct CostHookOf<D, std::void_t<decltype(D::kCostHook)>> {
+  static constexpr bool value = D::kCostHook;
+};
+template <class D, class = void>
+struct CarriedOf {
+  static constexpr int value = 0;
+};
+template <class D>
+struct CarriedOf<D, std::void_t<decltype(D::kCarried)>> {
+  static constexpr int value = D::kCarried;
+};
+
+// RK4, M substeps, one f call site (the four stages are a runtime loop) over the integrated
+// states; zr = the stage row for a model whose f reads it
 template <class Dyn, class S, class Tc>
-__device__ __forceinline__ void ode_rk4(const S* x0, const S* u, const OdeParams& op, S* xf, Tc& tc) {
-  constexpr int NX = Dyn::NX;
+__device__ __forceinline__ void ode_rk4(const S* x0, const S* u, const OdeParams& op, S* xf, Tc& tc,
+                                        const double* zr = nullptr) {
+  constexpr int NX = Dyn::NX - CarriedOf<Dyn>::value;
   S x[NX];
 #pragma unroll
   for (int i = 0; i < NX; ++i) x[i] = x0[i];
@@ -375,7 +475,10 @@ __device__ __forceinline__ void ode_rk4(const S* x0, const S* u, const OdeParams
     for (int i = 0; i < NX; ++i) xt[i] = x[i];
 #pragma unroll 1
     for (int st = 0; st < 4; ++st) {
-      Dyn::f(xt, u, op.par, k, tc);
+      if constexpr (StageParOf<Dyn>::value)
+        Dyn::f(xt, u, op.par, zr, k, tc);
+      else
+        Dyn::f(xt, u, op.par, k, tc);
       const double wa = (st == 0 || st == 3) ? 1.0 : 2.0;  // k1 + 2 k2 + 2 k3 + k4
       const double cn = (st == 2) ? h : 0.5 * h;           // next stage point x + c k
 #pragma unroll
@@ -402,6 +505,15 @@ struct OdeModel {
         if (!((Dyn::INDEP >> j) & 1u) || c == j) m |= 1ull << (c * NX + j);
     return m;
   }
+  static constexpr bool kStagePar = StageParOf<Dyn>::value, kCostHook = CostHookOf<Dyn>::value;
+  static constexpr int kCarried = CarriedOf<Dyn>::value;
+  // any of the three: RK4 is reached through interval().  A model without them keeps its direct
+  // ode_rk4 call: through interval() the compiler orders and allocates the existing units' code
+  // differently (device assembly against the direct call: kinematic bicycle 2876 differing lines,
+  // 6-state bicycle 2150, cart-pole 21,368, at the same register and scratch counts), while with
+  // the direct call -- and the cost through cost() / cost_derivs() / ref(), which reduce to the
+  // diagonal terms -- it is instruction for instruction what it was before the hooks
+  static constexpr bool kHooks = kStagePar || kCostHook || kCarried > 0;
   static constexpr unsigned long long AMASK = amask();
   static constexpr unsigned long long BMASK = (1ull << (NX * NU)) - 1;
   static constexpr bool kEvalInSearch = false;
@@ -452,28 +564,52 @@ struct OdeModel {
   // directly) -- sized so that the cache and the Riccati scan buffer fit the LDS together
   static constexpr int kTrigMaxM = Dyn::kTrigMaxM;
   static constexpr int kTrigSlots = Dyn::kTrigInput + Dyn::kTrigPerEval * 4 * kTrigMaxM;
+  // the interval map F: RK4 over the integrated states with the inputs f sees (a model with
+  // carried states: its effective inputs, then the carried states' transition)
+  template <class S, class Tc>
+  __device__ __forceinline__ static void interval(const ModelArgs& a, const Ctx& c, const S* z, S* xf, Tc& tc) {
+    if constexpr (kCarried > 0) {
+      S ue[NU];
+      Dyn::eff_input(z, ue);
+      ode_rk4<Dyn, S>(z, ue, a.op, xf, tc, c.zr);
+      Dyn::carry(ue, xf);
+    } else {
+      ode_rk4<Dyn, S>(z, z + NX, a.op, xf, tc, c.zr);
+    }
+  }
+  // reference of variable i in the diagonal node cost
+  __device__ __forceinline__ static double ref(const Ctx& c, int i) {
+    if constexpr (kCostHook)
+      return Dyn::cost_ref(c.zr, i);
+    else
+      return c.zr[i];
+  }
+  __device__ __forceinline__ static double cost(const ModelArgs& a, const Ctx& c, const double* z) {
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      const double d = z[i] - ref(c, i);
+      acc = fma(wgt(a, i) * d, d, acc);
+    }
+    if constexpr (kCostHook) acc += Dyn::cost_extra(a.op.par, c.zr, z);
+    return acc;
+  }
   template <class Tc>
   __device__ __forceinline__ static void value_tc(const ModelArgs& a, const Ctx& c, const double* z, double* xf,
                                                   double& q, Tc& tc) {
-    ode_rk4<Dyn, double>(z, z + NX, a.op, xf, tc);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < NZ; ++i) {
-      const double d = z[i] - c.zr[i];
-      acc = fma(wgt(a, i) * d, d, acc);
-    }
-    q = acc;
+    if constexpr (kHooks)
+      interval<double>(a, c, z, xf, tc);
+    else
+      ode_rk4<Dyn, double>(z, z + NX, a.op, xf, tc);
+    q = cost(a, c, z);
   }
   __device__ __forceinline__ static void value(const ModelArgs& a, const Ctx& c, const double* z, double* xf, double& q) {
     TrigDirect tc;
-    ode_rk4<Dyn, double>(z, z + NX, a.op, xf, tc);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < NZ; ++i) {
-      const double d = z[i] - c.zr[i];
-      acc = fma(wgt(a, i) * d, d, acc);
-    }
-    q = acc;
+    if constexpr (kHooks)
+      interval<double>(a, c, z, xf, tc);
+    else
+      ode_rk4<Dyn, double>(z, z + NX, a.op, xf, tc);
+    q = cost(a, c, z);
   }
   // F, q and their exact derivatives at z for the adjoint ln: the adjoint path where the model
   // has closed-form partials and its checkpoints fit this lane's LDS column, else hyper-dual passes
@@ -495,9 +631,10 @@ struct OdeModel {
 #pragma unroll
     for (int i = 0; i < NZ; ++i) {
       const double w2 = 2.0 * fs * wgt(a, i);
-      g[i] = w2 * (z[i] - c.zr[i]);
+      g[i] = w2 * (z[i] - ref(c, i));
       H[symix(i, i, NZ)] = w2;
     }
+    if constexpr (kCostHook) Dyn::cost_extra_derivs(a.op.par, c.zr, z, fs, g, H);
   }
   // Exact derivatives by forward sensitivities and stage adjoints (Dyn::kAdjoint: closed-form
   // partials of f).  Everything in RK4 but f is linear, so with mu_e the adjoint of stage e's f
@@ -687,14 +824,7 @@ struct OdeModel {
     } else {
       value(a, c, z, xf, q);
     }
-#pragma unroll
-    for (int i = 0; i < NH; ++i) H[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < NZ; ++i) {
-      const double w2 = 2.0 * fs * wgt(a, i);
-      g[i] = w2 * (z[i] - c.zr[i]);
-      H[symix(i, i, NZ)] = w2;
-    }
+    cost_derivs(a, c, z, fs, g, H);
 #pragma unroll
     for (int i = 0; i < NX * NX; ++i) A[i] = 0.0;
 #pragma unroll
@@ -719,10 +849,16 @@ struct OdeModel {
         for (int i = 0; i < NZ; ++i) zs[i] = HD{z[i], i == m ? 1.0 : 0.0, i == n ? 1.0 : 0.0, 0.0};
         if (cached) {
           TrigReplay rp{a.tc, a.tc_stride, Dyn::kTrigInput};
-          ode_rk4<Dyn, HD>(zs, zs + NX, a.op, xs, rp);
+          if constexpr (kHooks)
+            interval<HD>(a, c, zs, xs, rp);
+          else
+            ode_rk4<Dyn, HD>(zs, zs + NX, a.op, xs, rp);
         } else {
           TrigDirect td;
-          ode_rk4<Dyn, HD>(zs, zs + NX, a.op, xs, td);
+          if constexpr (kHooks)
+            interval<HD>(a, c, zs, xs, td);
+          else
+            ode_rk4<Dyn, HD>(zs, zs + NX, a.op, xs, td);
         }
         double s = 0.0;
 #pragma unroll

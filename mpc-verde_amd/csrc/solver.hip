@@ -91,7 +91,7 @@ hipError_t launch_rk4_sens(int B, int N, const StageParams& sp, const double* X,
 // workspace per thread: restoration (kernels.h RestoWs) for the unicycle and the ODE models, plus
 // the chain stash of the 6-state bicycle; none elsewhere
 int resto_ws_slots(int model, int nx, int nu) {
-  if (model != 1 && (model < 3 || model > 5)) return 0;  // the models with kResto: unicycle (1), ODE (3-5)
+  if (model != 1 && (model < 3 || model > 5) && model != 7) return 0;  // the models with kResto: unicycle (1), ODE (3-5, 7)
   return RestoWs::slots(nx, nu) + (model == 4 ? chain_ws_slots(nx, nu) : 0);  // model 4: OdeModel<DynBicycle>::kWsStash
 }
 
@@ -115,6 +115,7 @@ MPCX_DECLARE(linear4x2)
 MPCX_DECLARE(kin_bicycle)
 MPCX_DECLARE(dyn_bicycle)
 MPCX_DECLARE(cartpole)
+MPCX_DECLARE(path_bicycle)
 
 // horizons from which the unicycle's Riccati recursion runs as a log-depth scan (models.h
 // UnicycleScanModel): ceil(log2(N+1)) = 5 combine levels cost about as much as 25 chain steps
@@ -145,6 +146,7 @@ static int unicycle_scan_min_n() {
     if ((a).model == 3) return FN##_kin_bicycle(__VA_ARGS__);                     \
     if ((a).model == 4) return FN##_dyn_bicycle(__VA_ARGS__);                     \
     if ((a).model == 5) return FN##_cartpole(__VA_ARGS__);                        \
+    if ((a).model == 7) return FN##_path_bicycle(__VA_ARGS__);                    \
     return hipErrorInvalidValue;                                                  \
   } while (0)
 
@@ -171,11 +173,13 @@ hipError_t launch_shift(const SolveArgs& a, double* P, const double* W, double* 
 extern "C" int mpcx_diag_set_stamp_buffer(void* d_buf) {
   using namespace mpcx;
   return diag_set_stamps_unicycle(d_buf) | diag_set_stamps_unicycle_xfree(d_buf) | diag_set_stamps_unicycle_scan(d_buf) | diag_set_stamps_linear4(d_buf) | diag_set_stamps_linear5(d_buf) | diag_set_stamps_linear4x2(d_buf) |
-         diag_set_stamps_kin_bicycle(d_buf) | diag_set_stamps_dyn_bicycle(d_buf) | diag_set_stamps_cartpole(d_buf);
+         diag_set_stamps_kin_bicycle(d_buf) | diag_set_stamps_dyn_bicycle(d_buf) | diag_set_stamps_cartpole(d_buf) |
+         diag_set_stamps_path_bicycle(d_buf);
 }
 extern "C" int mpcx_diag_set_counter_buffer(void* d_buf) {
   using namespace mpcx;
   return diag_set_counters_unicycle(d_buf) | diag_set_counters_unicycle_xfree(d_buf) | diag_set_counters_unicycle_scan(d_buf) | diag_set_counters_linear4(d_buf) | diag_set_counters_linear5(d_buf) | diag_set_counters_linear4x2(d_buf) |
-         diag_set_counters_kin_bicycle(d_buf) | diag_set_counters_dyn_bicycle(d_buf) | diag_set_counters_cartpole(d_buf);
+         diag_set_counters_kin_bicycle(d_buf) | diag_set_counters_dyn_bicycle(d_buf) | diag_set_counters_cartpole(d_buf) |
+         diag_set_counters_path_bicycle(d_buf);
 }
 #endif

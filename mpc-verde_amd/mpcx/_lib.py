@@ -18,6 +18,7 @@ MODEL_LINEAR = 2
 MODEL_KIN_BICYCLE = 3
 MODEL_DYN_BICYCLE = 4
 MODEL_CARTPOLE = 5
+MODEL_PATH_BICYCLE = 7  # 6 is unassigned (include/mpcx.h)
 COST_QUADRATURE = 0
 COST_NODE = 1
 P_X0_XREF = 0

@@ -41,6 +41,18 @@ For the move-blocked QP (``lti.inverted_pendulum_qp``: kernel state (x, u_prev),
 stages' input held by the u_prev state) ``var["x", k]`` is the plant state and ``var["u", k]``
 the applied input -- the decision of a free stage, the held input of a blocked one -- as
 mpctools reports them for its ``Du = 0`` constraints.
+
+For the path-frame bicycle (``ode.path_bicycle_lane_keeping``: kernel state (y, phi, v, s) with s
+the steering applied in the previous interval, kernel input (d, a) with d its increment)
+``var["x", k]`` is the physical state (y, phi, v), ``var["u", k]`` the applied input (delta, a)
+and ``var["Du", k]`` the steering increment d, as mpctools reports a problem with ``Du`` bounds
+(``Trajectory Tracking/test2.py:55-59,122-143``).  ``uprev`` / ``par["uprev"]`` is the steering
+applied before stage 0.  It moves with the loop: ``saveguess(toffset >= 1)`` sets it to the
+steering the solution applies in interval ``toffset - 1``, and ``fixvar("x", 0, ...)`` after a
+solve sets it to the steering of interval 0 if nothing has moved it since that solve -- so the
+script's loop body (``solve``, ``saveguess``, ``fixvar("x", 0, var["x", 1])``) carries it from
+step to step, and so does a loop that only calls ``fixvar`` between solves.  Setting
+``par["uprev"]`` after a solve overrides both.
 """
 from __future__ import annotations
 
@@ -86,22 +98,25 @@ class ControlSolver:
     def __init__(self, ocp, x0=None, p=None, uprev=None, opts=None, device=0):
         self.ocp = ocp
         self._lin_blocked = isinstance(ocp, LinearOCP) and ocp.nx == 5 and ocp.nu == 1 and hasattr(ocp, "A_plant")
+        self._path = getattr(ocp, "model", None) == "path_bicycle"
         if ocp.param != "x0_stageref" and not self._lin_blocked:
             raise ValueError("nmpc supports only problems with param 'x0_stageref' (per-stage parameters) or the "
                              f"move-blocked QP of lti.inverted_pendulum_qp (got param={ocp.param!r})")
         self._solver = nlpsol("nmpc", "mi355x", ocp, opts or {}, device=device)
         N = ocp.N
-        self._nxu = (4, 1) if self._lin_blocked else (ocp.nx, ocp.nu)
+        self._nxu = (4, 1) if self._lin_blocked else (3, 2) if self._path else (ocp.nx, ocp.nu)
         nx, nu = self._nxu
         self.N = {"x": nx, "u": nu, "t": N}
         self._x0 = np.zeros(nx) if x0 is None else np.asarray(x0, float).reshape(nx)
-        if self._lin_blocked:
+        if self._lin_blocked or self._path:
             self._uprev = 0.0 if uprev is None else float(np.asarray(uprev, float).reshape(-1)[0])
+        if self._lin_blocked:
             self._p = None
         else:
             nzr = ocp.nx + ocp.nu
             self.N["p"] = nzr
             self._p = np.zeros((N, nzr)) if p is None else np.array(np.asarray(p, float).reshape(N, nzr))
+        self._uprev_due = False  # path bicycle: a solution's steering is waiting to become uprev
         self._w = None      # last solution (the solver's multiple-shooting layout)
         self._guess = None  # primal guess of the next solve
         self._f = np.nan
@@ -113,7 +128,7 @@ class ControlSolver:
     def _get_par(self, name):
         if name == "p" and self._p is not None:
             return list(self._p)
-        if name == "uprev" and self._lin_blocked:
+        if name == "uprev" and (self._lin_blocked or self._path):
             return [np.array([self._uprev])]
         raise KeyError(name)
 
@@ -123,7 +138,8 @@ class ControlSolver:
                 self._p[t if t is not None else slice(None)] = np.asarray(value, float).reshape(-1, self._p.shape[1])
             else:
                 self._p[t] = np.asarray(value, float).reshape(-1)
-        elif name == "uprev" and self._lin_blocked:
+        elif name == "uprev" and (self._lin_blocked or self._path):
+            self._uprev_due = False
             self._uprev = float(np.asarray(value, float).reshape(-1)[0])
         else:
             raise KeyError(name)
@@ -133,15 +149,22 @@ class ControlSolver:
         if name != "x" or t != 0 or index is not None:
             raise ValueError("fixvar: only fixvar('x', 0, value) (the initial state) is supported")
         self._x0 = np.asarray(val, float).reshape(self._nxu[0])
+        if self._path and self._uprev_due:  # a new initial state: one interval on, unless already moved
+            self._uprev = float(self._traj()[1][0, 0])
+            self._uprev_due = False
 
     # ---------------------------------------------------------------- solve
     def _params(self):
         if self._lin_blocked:
             from .lti import pendulum_params
             return pendulum_params(self.ocp, self._x0[None, :], self._uprev)
+        if self._path:  # the carried state: the steering applied before stage 0
+            return np.concatenate([self._x0, [self._uprev], self._p.reshape(-1)])[None, :]
         return np.concatenate([self._x0, self._p.reshape(-1)])[None, :]
 
     def solve(self):
+        self._s0 = self._uprev if self._path else None
+        self._uprev_due = self._path  # the solution's steering has not been carried into uprev yet
         r = self._solver.solve_batch(self._params(), w0=self._guess, want_lam=False)
         st = int(r["status"][0])
         self._w = r["w"][0]
@@ -164,6 +187,9 @@ class ControlSolver:
         Xs = np.concatenate([X[s:], np.repeat(X[-1:], s, axis=0)])[:N + 1]
         Us = np.concatenate([U[s:], np.repeat(U[-1:], s, axis=0)])[:N]
         self._guess = np.concatenate([Xs[0]] + [np.concatenate([Us[k], Xs[k + 1]]) for k in range(N)])[None, :]
+        if self._path and s >= 1:  # the steering the solution applies before the new stage 0
+            self._uprev = float(self._traj()[1][min(s, N) - 1, 0])
+            self._uprev_due = False
 
     # ---------------------------------------------------------------- solution
     def _traj(self):
@@ -177,6 +203,9 @@ class ControlSolver:
             free = np.asarray(ocp.tab).reshape(-1) == 0
             Ua = np.where(free[:, None], U, X[:N, 4:5])
             return X[:, 0:4], Ua
+        if self._path:  # physical states; applied steering s_k + d_k (s_0 = the parameter's)
+            sk = np.concatenate([[self._s0], X[1:N, 3]])
+            return X[:, 0:3], np.stack([sk + U[:, 0], U[:, 1]], axis=1)
         return X, U
 
     def _get_var(self, name):
@@ -187,6 +216,9 @@ class ControlSolver:
             return list(X)
         if name == "u":
             return list(U)
+        if name == "Du" and self._path:
+            N, nz = self.ocp.N, self.ocp.nx + self.ocp.nu
+            return [self._w[self.ocp.nx + nz * k:self.ocp.nx + nz * k + 1] for k in range(N)]
         raise KeyError(name)
 
 

@@ -100,7 +100,8 @@ def circular_reference(tau0, t, N, Delta=0.2):
 
 
 MODEL_IDS = {"unicycle": _lib.MODEL_UNICYCLE, "linear": _lib.MODEL_LINEAR, "kin_bicycle": _lib.MODEL_KIN_BICYCLE,
-             "dyn_bicycle": _lib.MODEL_DYN_BICYCLE, "cartpole": _lib.MODEL_CARTPOLE}
+             "dyn_bicycle": _lib.MODEL_DYN_BICYCLE, "cartpole": _lib.MODEL_CARTPOLE,
+             "path_bicycle": _lib.MODEL_PATH_BICYCLE}
 
 
 # IPOPT termination / recovery options the spec carries (IPOPT's names); values left out take

@@ -17,6 +17,13 @@ same IPM kernel with exact derivatives (``csrc/ode.h``).  Parity: against the CP
 * ``cartpole``     x = (p, p', phi, phi'), u = F; M = m = 1, L = 0.5, g = 9.81, c = 10: linearised
   at phi = 0 it is the reference's Ac, Bc (``inverted_pendulum_single_shooting_mpctools.py:19-23``).
   Config 5 variant ("swing-up, N=100"); cost (1.2 (p - p_ref))^2 + phi^2 + (0.01 F)^2 (:33-36).
+* ``path_bicycle`` x = (y, phi, v, s), u = (d, a): the path-frame kinematic bicycle of the
+  lane-keeping study (``Trajectory Tracking/test2.py:103-112``) with its steering-rate limit
+  (:35-36, 55-59).  s is the steering applied in the previous interval and d its increment: the
+  interval's steering delta = s + d is held over the RK4 substeps and s+ = delta exactly, so the
+  script's ``Du`` bound is the box on d and its steering bound the box on s.  Stage rows
+  (yt, phit, vdes, kappa, 0, a_ref): yt, phit and the path curvature enter the dynamics; the
+  cost adds w_z (tan(delta) - L kappa)^2 to the diagonal terms (:42-49).  par = (L, c1, c2, w_z).
 """
 from __future__ import annotations
 
@@ -28,7 +35,7 @@ import numpy as np
 from . import _lib
 
 MODELS = {"kin_bicycle": (_lib.MODEL_KIN_BICYCLE, 3, 2), "dyn_bicycle": (_lib.MODEL_DYN_BICYCLE, 6, 2),
-          "cartpole": (_lib.MODEL_CARTPOLE, 4, 1)}
+          "cartpole": (_lib.MODEL_CARTPOLE, 4, 1), "path_bicycle": (_lib.MODEL_PATH_BICYCLE, 4, 2)}
 DYN_BICYCLE_PAR = (1200.0, 1.5, 2.0, 55000.0, 1350.0)  # m, a, b, Ca, Jz
 CARTPOLE_PAR = (1.0, 1.0, 0.5, 9.81, 10.0)              # M, m, L, g, c
 
@@ -61,6 +68,15 @@ class OdeOCP:
             raise ValueError("ODE models use the node cost")
         if self.formulation not in ("multiple_shooting", "single_shooting"):
             raise ValueError(f"unknown formulation {self.formulation!r}")
+        if self.model == "path_bicycle":
+            if len(self.par) != 4 or not all(math.isfinite(float(v)) for v in self.par):
+                raise ValueError("path_bicycle: par = (L, c1, c2, w_z), all finite")
+            if not self.par[0] > 0:
+                raise ValueError("path_bicycle: L = par[0] must be > 0")
+            if self.param != "x0_stageref":
+                raise ValueError("path_bicycle: the stage rows enter the dynamics, param must be 'x0_stageref'")
+            if self.formulation != "multiple_shooting":
+                raise ValueError("path_bicycle: multiple shooting only (the steering bound is a state bound)")
 
     @property
     def nx(self):
@@ -166,3 +182,86 @@ def cartpole_swingup(N=100, T=0.01, M=1, u_max=200.0, formulation="multiple_shoo
     inf = math.inf
     return OdeOCP(model="cartpole", N=N, T=T, M=M, Q=(1.44, 0.0, 1.0, 0.0), R=(1e-4,), u_lb=(-u_max,), u_ub=(u_max,),
                   x_lb=(-inf,) * 4, x_ub=(inf,) * 4, par=CARTPOLE_PAR, param="x0_xref", formulation=formulation)
+
+
+# ---------------------------------------------------------------------------- path-frame bicycle
+def path_bicycle_lane_keeping(N=20, T=0.05, L=3.5, steer="bicycle", rate_max=0.1225, delta_max=0.384, a_max=2.0):
+    """The lane-keeping NMPC of ``Trajectory Tracking/test2.py`` (constants :19-36, cost :42-49,
+    bounds :55-59, RK4 with M = 1 :118): weights (1.75, 2.5, 2.5)/(N+1) on (y - yt, phi - phit,
+    v - vdes), 0.4/(N+1) on a - a_ref, 10/(N+1) on (tan(delta) - L kappa)^2; |delta| <= delta_max
+    (the box on the carried state s), |delta_k - delta_{k-1}| <= rate_max (the box on d), |a| <= a_max.
+
+    ``steer="bicycle"`` (default) turns with tan(delta) / L; ``steer="as_written"`` with the
+    script's tan(delta / L) (:109) -- the same kernel, other constants in ``par``."""
+    if steer not in ("bicycle", "as_written"):
+        raise ValueError(f"steer: 'bicycle' or 'as_written' (got {steer!r})")
+    L = float(L)
+    if not L > 0:
+        raise ValueError("L must be > 0")
+    c1, c2 = (1.0, 1.0 / L) if steer == "bicycle" else (1.0 / L, 1.0)
+    n1 = N + 1.0
+    inf = math.inf
+    return OdeOCP(model="path_bicycle", N=N, T=T, M=1, Q=(1.75 / n1, 2.5 / n1, 2.5 / n1, 0.0), R=(0.0, 0.4 / n1),
+                  u_lb=(-float(rate_max), -float(a_max)), u_ub=(float(rate_max), float(a_max)),
+                  x_lb=(-inf, -inf, -inf, -float(delta_max)), x_ub=(inf, inf, inf, float(delta_max)),
+                  par=(L, c1, c2, 10.0 / n1))
+
+
+def path_bicycle_references(xtraj, ytraj, vdes, t, N, Delta=0.05, as_written=False):
+    """Stage rows (N, 6) = (yt, phit, vdes, kappa, 0, a_ref = 0) of step t from the path rows
+    (``test2.py:79-99``), with the script's boundary rules.  The script fixes Nsim = 500, the
+    number of rows of its lane_change.csv; here Nsim is ``len(xtraj)``, so the rules of the path's
+    end coincide with the script's only when the caller passes exactly the rows the script walks
+    (a longer or shorter path ends where its own rows end).  Row
+    i = t + k past the end repeats the last row's y and the last segment's heading; i = 0 has
+    heading 0, the others the heading of the segment arriving at i; the curvature slot of i < 2 is
+    a placeholder, and from i = Nsim - 1 on it holds the value of i = Nsim - 2 (the script copies the
+    row above, which at k = 0 is the last row left from the step before: the same value) while
+    vdes holds its last row.
+
+    ``as_written=False``: kappa is the signed curvature (x' y'' - y' x'') / (x'^2 + y'^2)^1.5 from
+    the script's second differences and centred first differences, 0 in the placeholder rows.
+
+    ``as_written=True``: the rows as the script's own functions read them.  It stores vdes in
+    slot 2 and the norm of the second differences in slot 3 (:91,98; placeholder 1), but its
+    stage cost and model take slot 2 as kappa and slot 3 as vdes (:45-46,106) -- so here kappa =
+    the csv's uref and vdes = |(x'', y'')|."""
+    x, y, v = (np.asarray(c, float) for c in (xtraj, ytraj, vdes))
+    n = len(x)
+    rows = np.zeros((N, 6))
+    for k in range(N):
+        i = t + k
+        if i > n - 1:
+            rows[k, 0] = y[n - 1]
+            rows[k, 1] = np.arctan2(y[n - 1] - y[n - 2], x[n - 1] - x[n - 2])
+        elif i == 0:
+            rows[k, 0] = y[0]
+        else:
+            rows[k, 0] = y[i]
+            rows[k, 1] = np.arctan2(y[i] - y[i - 1], x[i] - x[i - 1])
+        j = min(i, n - 2)  # the second differences' row (held from n - 2 on)
+        if j < 2:
+            dd = 1.0 if as_written else 0.0
+        else:
+            ddx = (x[j - 1] - 2 * x[j] + x[j + 1]) / Delta**2
+            ddy = (y[j - 1] - 2 * y[j] + y[j + 1]) / Delta**2
+            if as_written:
+                dd = float(np.linalg.norm(np.array([ddx, ddy])))
+            else:
+                dx, dy = (x[j + 1] - x[j - 1]) / (2 * Delta), (y[j + 1] - y[j - 1]) / (2 * Delta)
+                dd = (dx * ddy - dy * ddx) / (dx * dx + dy * dy) ** 1.5
+        vd = v[i] if i <= n - 2 else v[n - 1]
+        rows[k, 2], rows[k, 3] = (dd, vd) if as_written else (vd, dd)
+    return rows
+
+
+def path_bicycle_params(ocp, x, delta_prev, rows):
+    """P (B, 4 + 6 N) from the physical states x (B, 3) = (y, phi, v), the steering applied in
+    the previous interval delta_prev (scalar or (B,); mpctools' ``uprev``) and the stage rows
+    (N, 6) or (B, N, 6) of :func:`path_bicycle_references`."""
+    x = np.atleast_2d(np.asarray(x, np.float64))
+    if x.shape[1] != 3:
+        raise ValueError("x: (B, 3) physical states (y, phi, v)")
+    B = x.shape[0]
+    s = np.broadcast_to(np.asarray(delta_prev, np.float64).reshape(-1, 1), (B, 1))
+    return ocp.params(np.concatenate([x, s], axis=1), rows)
