@@ -89,23 +89,16 @@ struct DeviceScope {
 
 // (nx, nu) fixed by the model; the linear model takes them from the spec
 int nx_of(const mpcx_spec& s) {
-  switch (s.model) {
-    case MPCX_MODEL_UNICYCLE: case MPCX_MODEL_KIN_BICYCLE: return 3;
-    case MPCX_MODEL_DYN_BICYCLE: return 6;
-    case MPCX_MODEL_CARTPOLE: case MPCX_MODEL_PATH_BICYCLE: return 4;
-    default: return s.nx;
-  }
+  const mpcx::ModelInfo* m = mpcx::model_info(s.model);
+  return m && m->fixed_dims ? m->units[0]->nx : s.nx;
 }
 int nu_of(const mpcx_spec& s) {
-  switch (s.model) {
-    case MPCX_MODEL_UNICYCLE: case MPCX_MODEL_KIN_BICYCLE: case MPCX_MODEL_DYN_BICYCLE:
-    case MPCX_MODEL_PATH_BICYCLE: return 2;
-    case MPCX_MODEL_CARTPOLE: return 1;
-    default: return s.nu;
-  }
+  const mpcx::ModelInfo* m = mpcx::model_info(s.model);
+  return m && m->fixed_dims ? m->units[0]->nu : s.nu;
 }
 bool is_ode(int model) {
-  return (model >= MPCX_MODEL_KIN_BICYCLE && model <= MPCX_MODEL_CARTPOLE) || model == MPCX_MODEL_PATH_BICYCLE;
+  const mpcx::ModelInfo* m = mpcx::model_info(model);
+  return m && m->ode;
 }
 
 mpcx::OdeParams ode_params(const mpcx_spec& s) {
@@ -251,7 +244,8 @@ const char* mpcx_source_hash(void) {
 
 int mpcx_default_spec(mpcx_spec* s, int32_t model, int32_t N) {
   if (!s) return fail(MPCX_EINVAL, "null spec");
-  if (model != MPCX_MODEL_UNICYCLE && !is_ode(model)) return fail(MPCX_EINVAL, "unknown model");
+  const mpcx::ModelInfo* m = mpcx::model_info(model);
+  if (!m || !m->fixed_dims) return fail(MPCX_EINVAL, "unknown model");  // (the linear model has no defaults)
   std::memset(s, 0, sizeof *s);
   // Casadi/multiple_shooting_casadi.py:30-45, 78-84, 101, 188-196
   s->model = model;
@@ -271,8 +265,8 @@ int mpcx_default_spec(mpcx_spec* s, int32_t model, int32_t N) {
     s->lbx[i] = -1e20;
     s->ubx[i] = 1e20;
   }
-  s->nx = 3;
-  s->nu = 2;
+  s->nx = nx_of(*s);
+  s->nu = nu_of(*s);
   s->warm_mu_init = 1e-4;
   s->warm_bound_push = 1e-4;
   s->warm_mult_push = 1e-4;
@@ -297,8 +291,6 @@ int mpcx_default_spec(mpcx_spec* s, int32_t model, int32_t N) {
     s->cost = MPCX_COST_NODE;
     s->param_layout = MPCX_P_X0_STAGEREF;
     s->M = 1;
-    s->nx = nx_of(*s);
-    s->nu = nu_of(*s);
     for (int i = 0; i < 8; ++i) {
       s->Q[i] = s->R[i] = 0.0;
       s->lbx[i] = -1e20;
@@ -345,12 +337,13 @@ int mpcx_default_spec(mpcx_spec* s, int32_t model, int32_t N) {
 
 int mpcx_create(const mpcx_spec* s, mpcx_handle** out) {
   if (!s || !out) return fail(MPCX_EINVAL, "null argument");
-  if (s->model != MPCX_MODEL_UNICYCLE && s->model != MPCX_MODEL_LINEAR && !is_ode(s->model))
-    return fail(MPCX_EINVAL, "unknown model");
+  if (!mpcx::model_info(s->model)) return fail(MPCX_EINVAL, "unknown model");
   if (is_ode(s->model) && s->cost != MPCX_COST_NODE) return fail(MPCX_EINVAL, "ODE models use MPCX_COST_NODE");
-  if (s->model == MPCX_MODEL_LINEAR &&
-      !((s->nx == 4 && s->nu == 1) || (s->nx == 5 && s->nu == 1) || (s->nx == 4 && s->nu == 2)))
-    return fail(MPCX_EINVAL, "linear model: (nx, nu) must be (4, 1), (5, 1) or (4, 2)");
+  mpcx::SolveArgs shape{};  // (only the linear model's (nx, nu) can be without a solve unit)
+  shape.model = s->model;
+  shape.nx = s->nx;
+  shape.nu = s->nu;
+  if (!mpcx::model_ops(shape)) return fail(MPCX_EINVAL, "linear model: (nx, nu) must be (4, 1), (5, 1) or (4, 2)");
   if (s->N < 1 || s->N > 255) return fail(MPCX_EINVAL, "N must be in [1, 255]");
   if (s->M < 1 || s->M > 64) return fail(MPCX_EINVAL, "M must be in [1, 64]");
   if ((s->model == MPCX_MODEL_UNICYCLE || is_ode(s->model)) && !(s->T > 0)) return fail(MPCX_EINVAL, "T must be > 0");
@@ -512,9 +505,14 @@ static int check_model_ready(const mpcx_handle* h, int B) {
   return 0;
 }
 
-static mpcx::SolveArgs make_args(const mpcx_handle* h, int B, const double* P, const double* w0, const double* lam0,
-                                 const double* lamx0, const double* lbw, const double* ubw, double* w, double* f,
-                                 double* lam, double* lamx, int32_t* st, int32_t* it) {
+// device pointers of one launch (SolveArgs has their meaning); the rest of SolveArgs comes from the handle
+struct SolveIO {
+  const double *P = nullptr, *w0 = nullptr, *lam0 = nullptr, *lamx0 = nullptr;
+  double *w = nullptr, *f = nullptr, *lam = nullptr, *lamx = nullptr;
+  int32_t *status = nullptr, *iters = nullptr;
+};
+
+static mpcx::SolveArgs make_args(const mpcx_handle* h, int B, const SolveIO& io) {
   mpcx::SolveArgs a{};
   a.B = B;
   a.model = h->spec.model;
@@ -552,23 +550,39 @@ static mpcx::SolveArgs make_args(const mpcx_handle* h, int B, const double* P, c
   }
   a.sp = stage_params(h->spec);
   a.op = ode_params(h->spec);
-  a.P = P;
-  a.w0 = w0;
-  a.lam0 = lam0;
-  a.lamx0 = lamx0;
-  a.warm = (lam0 || lamx0) ? 1 : 0;
+  a.P = io.P;
+  a.w0 = io.w0;
+  a.lam0 = io.lam0;
+  a.lamx0 = io.lamx0;
+  a.warm = (io.lam0 || io.lamx0) ? 1 : 0;
   a.mu_init = h->spec.warm_mu_init;
   a.bound_push = h->spec.warm_bound_push;
   a.mult_push = h->spec.warm_mult_push;
-  a.lbw = lbw;
-  a.ubw = ubw;
+  a.lbw = h->d_lbw;  // the spec's bounds (mpcx_solve_batch: the call's)
+  a.ubw = h->d_ubw;
   a.xbnd = h->spec_xbnd;
-  a.w_out = w;
-  a.f_out = f;
-  a.lam_out = lam;
-  a.lamx_out = lamx;
-  a.status = st;
-  a.iters = it;
+  a.w_out = io.w;
+  a.f_out = io.f;
+  a.lam_out = io.lam;
+  a.lamx_out = io.lamx;
+  a.status = io.status;
+  a.iters = io.iters;
+  return a;
+}
+
+// the fused receding-horizon launch of mpcx_step_dev / mpcx_run_dev: the start (cold: X_k = x0, U = 0; duals:
+// from the multipliers too) and the update of P and the warm start in place; `io` holds the outputs
+static mpcx::SolveArgs make_step_args(const mpcx_handle* h, int B, double* d_P, double* d_w0, double* d_lam_g0,
+                                      double* d_lam_x0, bool cold, bool duals, SolveIO io) {
+  io.P = d_P;
+  io.w0 = cold ? nullptr : d_w0;
+  io.lam0 = duals ? d_lam_g0 : nullptr;
+  io.lamx0 = duals ? d_lam_x0 : nullptr;
+  mpcx::SolveArgs a = make_args(h, B, io);
+  a.P_next = d_P;
+  a.w0_next = d_w0;
+  a.lam0_next = d_lam_g0;
+  a.lamx0_next = d_lam_x0;
   return a;
 }
 
@@ -577,16 +591,16 @@ int mpcx_launch_shape(const mpcx_handle* h, int32_t B, int32_t* lanes, int32_t* 
   if (!h) return fail(MPCX_EINVAL, "null handle");
   if (B < 1) return fail(MPCX_EINVAL, "B < 1");
   if (kernel && kernel_len < 1) return fail(MPCX_EINVAL, "kernel_len < 1");
-  const mpcx::SolveArgs a = make_args(h, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr);
+  const mpcx::SolveArgs a = make_args(h, B, {});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
   int G = 0, R = 0;
-  const char* model = nullptr;
-  if (mpcx::solve_shape(a, &G, &R, &model) != hipSuccess || !model) return fail(MPCX_EINVAL, "no kernel for this model");
+  ops->solve_shape(a, &G, &R);
   if (lanes) *lanes = G;
   if (replicas) *replicas = R;
   if (kernel) {
     const int n = snprintf(kernel, (size_t)kernel_len, "void mpcx::solve_kernel<%s, %d, false, %d>(mpcx::SolveArgs)",
-                           model, G, R);
+                           ops->name, G, R);
     if (n < 0 || n >= kernel_len) return fail(MPCX_EINVAL, "kernel name buffer too small");
   }
   return 0;
@@ -595,11 +609,12 @@ int mpcx_launch_shape(const mpcx_handle* h, int32_t B, int32_t* lanes, int32_t* 
 // launch the solve with the restoration workspace of the model (grown on demand; freed only
 // after the device is idle, since a queued launch may still use it)
 static int solve_launch(mpcx_handle* h, mpcx::SolveArgs& a, hipStream_t stream) {
-  const int slots = mpcx::resto_ws_slots(a.model, a.nx, a.nu);
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  const int slots = ops->ws_slots();
   if (slots > 0) {  // (the 6-state bicycle's chain stash needs it with restoration off too)
     int Gk = 0, R = 0;  // the launch's lanes per instance (the kernel's grid, kernels.h solve_shape)
-    const char* kname = nullptr;
-    if (mpcx::solve_shape(a, &Gk, &R, &kname) != hipSuccess) return fail(MPCX_EINVAL, "no kernel for this model");
+    ops->solve_shape(a, &Gk, &R);
     const int G = Gk * R;
     const long bs = G > 64 ? G : 64;
     const long threads = ((long)a.B * G + bs - 1) / bs * bs;
@@ -633,9 +648,9 @@ static int solve_launch(mpcx_handle* h, mpcx::SolveArgs& a, hipStream_t stream) 
     a.pc_epoch = (h->pc_epoch += 1);
     a.pc_gen = h->pc_gen;
   }
-  HIPCHK(mpcx::launch_solve(a, stream));
+  HIPCHK(ops->solve(a, stream));
   // instances parked at a failed line search continue in the resume launch (restoration)
-  if (a.restoration) HIPCHK(mpcx::launch_resume(a, stream));
+  if (a.restoration) HIPCHK(ops->resume(a, stream));
   return 0;
 }
 
@@ -647,10 +662,10 @@ int mpcx_solve_batch_dev(mpcx_handle* h, int32_t B, const double* d_P, const dou
   if (B == 0) return 0;
   if (int r = check_model_ready(h, B)) return r;
   DEVICE_SCOPE(h->spec.device);
-  mpcx::SolveArgs a = make_args(h, B, d_P, d_w0, d_lam_g0, d_lam_x0, h->d_lbw, h->d_ubw, d_w_out, d_f_out, d_lam_g,
-                                d_lam_x, d_status, d_iters);
-  if (int r = solve_launch(h, a, (hipStream_t)stream)) return r;
-  return 0;
+  mpcx::SolveArgs a = make_args(h, B, {.P = d_P, .w0 = d_w0, .lam0 = d_lam_g0, .lamx0 = d_lam_x0, .w = d_w_out,
+                                       .f = d_f_out, .lam = d_lam_g, .lamx = d_lam_x, .status = d_status,
+                                       .iters = d_iters});
+  return solve_launch(h, a, (hipStream_t)stream);
 }
 
 int mpcx_step_dev(mpcx_handle* h, int32_t B, double* d_P, double* d_w0, double* d_lam_g0, double* d_lam_x0,
@@ -664,15 +679,10 @@ int mpcx_step_dev(mpcx_handle* h, int32_t B, double* d_P, double* d_w0, double* 
   DEVICE_SCOPE(h->spec.device);
   const bool cold = flags & MPCX_STEP_COLD;
   const bool duals = !cold && !(flags & MPCX_STEP_PRIMAL_ONLY);
-  mpcx::SolveArgs a = make_args(h, B, d_P, cold ? nullptr : d_w0, duals ? d_lam_g0 : nullptr,
-                                duals ? d_lam_x0 : nullptr, h->d_lbw, h->d_ubw, d_w_out, d_f_out, d_lam_g, d_lam_x,
-                                d_status, d_iters);
-  a.P_next = d_P;
-  a.w0_next = d_w0;
-  a.lam0_next = d_lam_g0;
-  a.lamx0_next = d_lam_x0;
-  if (int r = solve_launch(h, a, (hipStream_t)stream)) return r;
-  return 0;
+  mpcx::SolveArgs a = make_step_args(h, B, d_P, d_w0, d_lam_g0, d_lam_x0, cold, duals,
+                                     {.w = d_w_out, .f = d_f_out, .lam = d_lam_g, .lamx = d_lam_x,
+                                      .status = d_status, .iters = d_iters});
+  return solve_launch(h, a, (hipStream_t)stream);
 }
 
 int mpcx_run_dev(mpcx_handle* h, int32_t B, int32_t K, double* d_P, double* d_w0, double* d_lam_g0, double* d_lam_x0,
@@ -688,19 +698,14 @@ int mpcx_run_dev(mpcx_handle* h, int32_t B, int32_t K, double* d_P, double* d_w0
   DEVICE_SCOPE(h->spec.device);
   const bool cold = flags & MPCX_STEP_COLD;
   const bool duals = !(flags & MPCX_STEP_PRIMAL_ONLY) && (d_lam_g0 || d_lam_x0);
-  mpcx::SolveArgs a = make_args(h, B, d_P, cold ? nullptr : d_w0, (duals && !cold) ? d_lam_g0 : nullptr,
-                                (duals && !cold) ? d_lam_x0 : nullptr, h->d_lbw, h->d_ubw, d_w_out, d_f_out, d_lam_g,
-                                d_lam_x, d_status, d_iters);
-  a.P_next = d_P;
-  a.w0_next = d_w0;
-  a.lam0_next = d_lam_g0;
-  a.lamx0_next = d_lam_x0;
+  mpcx::SolveArgs a = make_step_args(h, B, d_P, d_w0, d_lam_g0, d_lam_x0, cold, duals && !cold,
+                                     {.w = d_w_out, .f = d_f_out, .lam = d_lam_g, .lamx = d_lam_x,
+                                      .status = d_status, .iters = d_iters});
   a.steps = K;
   a.warm_next = duals ? 1 : 0;
   a.Pseq = d_Pseq;
   a.tabseq = d_tabseq;
-  if (int r = solve_launch(h, a, (hipStream_t)stream)) return r;
-  return 0;
+  return solve_launch(h, a, (hipStream_t)stream);
 }
 
 int mpcx_solve_batch(mpcx_handle* h, int32_t B, const double* P, const double* w0, const double* lam_g0,
@@ -741,9 +746,12 @@ int mpcx_solve_batch(mpcx_handle* h, int32_t B, const double* P, const double* w
   if (w0) HIPCHK(hipMemcpyAsync(h->d_w0, w0, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
   if (lam_g0) HIPCHK(hipMemcpyAsync(h->d_lam0, lam_g0, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
   if (lam_x0) HIPCHK(hipMemcpyAsync(h->d_lamx0, lam_x0, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, h->d_P, w0 ? h->d_w0 : nullptr, lam_g0 ? h->d_lam0 : nullptr,
-                                lam_x0 ? h->d_lamx0 : nullptr, dl, du, h->d_w, h->d_f, (lam_g ? h->d_lam : nullptr),
-                                (lam_x ? h->d_lamx : nullptr), h->d_status, h->d_iters);
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P, .w0 = w0 ? h->d_w0 : nullptr, .lam0 = lam_g0 ? h->d_lam0 : nullptr,
+                                       .lamx0 = lam_x0 ? h->d_lamx0 : nullptr, .w = h->d_w, .f = h->d_f,
+                                       .lam = lam_g ? h->d_lam : nullptr, .lamx = lam_x ? h->d_lamx : nullptr,
+                                       .status = h->d_status, .iters = h->d_iters});
+  a.lbw = dl;
+  a.ubw = du;
   a.xbnd = call_xbnd;
   if (int r = solve_launch(h, a, s)) return r;
   if (lam_x) HIPCHK(hipMemcpyAsync(lam_x, h->d_lamx, (size_t)B * h->nw * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -754,7 +762,7 @@ int mpcx_solve_batch(mpcx_handle* h, int32_t B, const double* P, const double* w
   if (iters) HIPCHK(hipMemcpyAsync(iters, h->d_iters, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (g_out) {  // constraint values at the solution (constraints kernel on the device)
-    HIPCHK(mpcx::launch_constraints(a, h->d_w, h->d_g, s));
+    HIPCHK(mpcx::model_ops(a)->constraints(a, h->d_w, h->d_g, s));  // (the unit that just solved)
     HIPCHK(hipMemcpyAsync(g_out, h->d_g, (size_t)B * h->ng * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
   }
@@ -772,9 +780,9 @@ int mpcx_plant_step(mpcx_handle* h, int32_t B, const double* P, const double* u,
   double *dP = h->d_P, *dU = h->d_u, *dX = h->d_x, *dQ = h->d_q;
   HIPCHK(hipMemcpyAsync(dP, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dU, u, (size_t)B * nu * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, dP, nullptr, nullptr, nullptr, h->d_lbw, h->d_ubw, nullptr, nullptr, nullptr,
-                                nullptr, nullptr, nullptr);
-  HIPCHK(mpcx::launch_plant(a, dU, dX, dQ, s));
+  const mpcx::SolveArgs a = make_args(h, B, {.P = dP});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  HIPCHK(ops ? ops->plant(a, dU, dX, dQ, s) : hipErrorInvalidValue);
   HIPCHK(hipMemcpyAsync(xf, dX, (size_t)B * nx * sizeof(double), hipMemcpyDeviceToHost, s));
   if (qf) HIPCHK(hipMemcpyAsync(qf, dQ, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -790,10 +798,10 @@ int mpcx_shift_dev(mpcx_handle* h, int32_t B, double* d_P, const double* d_w, do
     return fail(MPCX_EINVAL, "multiplier shift needs both source and destination");
   if (int r = check_model_ready(h, B)) return r;
   DEVICE_SCOPE(h->spec.device);
-  mpcx::SolveArgs a = make_args(h, B, d_P, nullptr, nullptr, nullptr, h->d_lbw, h->d_ubw, nullptr, nullptr, nullptr,
-                                nullptr, nullptr, nullptr);
-  HIPCHK(mpcx::launch_shift(a, d_P, d_w, d_w0_next, d_lam_g, d_lam_g0_next, d_lam_x, d_lam_x0_next,
-                            (hipStream_t)stream));
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  HIPCHK(ops ? ops->shift(a, d_P, d_w, d_w0_next, d_lam_g, d_lam_g0_next, d_lam_x, d_lam_x0_next, (hipStream_t)stream)
+             : hipErrorInvalidValue);
   return 0;
 }
 

@@ -1,7 +1,7 @@
 // kernels.h -- fused batched interior-point solve of multiple-shooting MPC NLPs on gfx950
 // (MI355X), and the per-model plant / shift / constraint kernels.  Included by one
 // translation unit per stage model (solve_<model>.hip, MPCX_INSTANTIATE), so the models
-// compile in parallel; solver.hip holds the dispatch and the RK4+Jacobian sweep.
+// compile in parallel; solver.hip holds the model registry and the RK4+Jacobian sweep.
 //
 // Replaces, for B independent instances at once, the reference's
 //   sol = solver(x0=w0, lbx, ubx, lbg, ubg, p)     Casadi/multiple_shooting_casadi.py:235-242
@@ -2716,56 +2716,36 @@ static void solve_shape(const SolveArgs& a, int* G, int* R) {
   }
 }
 
-template <class Model>
+// the solve launch (kResume = false) and the resume launch of the models with a restoration phase
+// (kResume = true: same grid, the parked groups only; nothing to launch for the other models)
+template <class Model, bool kResume>
 static hipError_t launch_solve_model(const SolveArgs& a, hipStream_t stream) {
-  // lane group: the smallest power of two holding nodes 0..N; G > 64 spans G/64 waves.
-  // A batch too small to give every SIMD a wave gets wider groups (up to one instance per
-  // wave): the per-wave instruction stream is the same, but a wave then runs only its own
-  // instance's iterations, not the maximum over the instances it holds (config 2: +5 %
-  // solves/s in multi-step launches).  spec.group_policy = 1 keeps the narrowest group.
-  // (Measured and not adopted: collectives over the 32 lanes of config 2's nodes on the same
-  // 64-lane grid -- no gain)
-  int Gk, R;
-  solve_shape<Model>(a, &Gk, &R);
-  const int G = Gk * R;  // lanes per instance on the grid
-  const long threads = (long)a.B * G;
-  const int bs = G > 64 ? G : 64;
-  const int blocks = (int)((threads + bs - 1) / bs);
-  if constexpr (ReplicateOf<Model>::value)
-    if (R == 2) {
-      hipLaunchKernelGGL((solve_kernel<Model, 32, false, 2>), dim3(blocks), dim3(64), 0, stream, a);
-      return hipGetLastError();
-    }
-  if (G == 16) hipLaunchKernelGGL((solve_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a);
-  else if (G == 32) hipLaunchKernelGGL((solve_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a);
-  else if (G == 64) hipLaunchKernelGGL((solve_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a);
-  else if (G == 128) hipLaunchKernelGGL((solve_kernel<Model, 128>), dim3(blocks), dim3(128), 0, stream, a);
-  else hipLaunchKernelGGL((solve_kernel<Model, 256>), dim3(blocks), dim3(256), 0, stream, a);
-  return hipGetLastError();
-}
-
-// the resume launch (models with a restoration phase): same grid, the parked groups only
-template <class Model>
-static hipError_t launch_resume_model(const SolveArgs& a, hipStream_t stream) {
-  if constexpr (!RestoOf<Model>::value) {
+  if constexpr (kResume && !RestoOf<Model>::value) {
     return hipSuccess;
   } else {
+    // lane group: the smallest power of two holding nodes 0..N; G > 64 spans G/64 waves.
+    // A batch too small to give every SIMD a wave gets wider groups (up to one instance per
+    // wave): the per-wave instruction stream is the same, but a wave then runs only its own
+    // instance's iterations, not the maximum over the instances it holds (config 2: +5 %
+    // solves/s in multi-step launches).  spec.group_policy = 1 keeps the narrowest group.
+    // (Measured and not adopted: collectives over the 32 lanes of config 2's nodes on the same
+    // 64-lane grid -- no gain)
     int Gk, R;
     solve_shape<Model>(a, &Gk, &R);
-    const int G = Gk * R;
+    const int G = Gk * R;  // lanes per instance on the grid
     const long threads = (long)a.B * G;
     const int bs = G > 64 ? G : 64;
     const int blocks = (int)((threads + bs - 1) / bs);
     if constexpr (ReplicateOf<Model>::value)
       if (R == 2) {
-        hipLaunchKernelGGL((solve_kernel<Model, 32, true, 2>), dim3(blocks), dim3(64), 0, stream, a);
+        hipLaunchKernelGGL((solve_kernel<Model, 32, kResume, 2>), dim3(blocks), dim3(64), 0, stream, a);
         return hipGetLastError();
       }
-    if (G == 16) hipLaunchKernelGGL((solve_kernel<Model, 16, true>), dim3(blocks), dim3(64), 0, stream, a);
-    else if (G == 32) hipLaunchKernelGGL((solve_kernel<Model, 32, true>), dim3(blocks), dim3(64), 0, stream, a);
-    else if (G == 64) hipLaunchKernelGGL((solve_kernel<Model, 64, true>), dim3(blocks), dim3(64), 0, stream, a);
-    else if (G == 128) hipLaunchKernelGGL((solve_kernel<Model, 128, true>), dim3(blocks), dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL((solve_kernel<Model, 256, true>), dim3(blocks), dim3(256), 0, stream, a);
+    if (G == 16) hipLaunchKernelGGL((solve_kernel<Model, 16, kResume>), dim3(blocks), dim3(64), 0, stream, a);
+    else if (G == 32) hipLaunchKernelGGL((solve_kernel<Model, 32, kResume>), dim3(blocks), dim3(64), 0, stream, a);
+    else if (G == 64) hipLaunchKernelGGL((solve_kernel<Model, 64, kResume>), dim3(blocks), dim3(64), 0, stream, a);
+    else if (G == 128) hipLaunchKernelGGL((solve_kernel<Model, 128, kResume>), dim3(blocks), dim3(128), 0, stream, a);
+    else hipLaunchKernelGGL((solve_kernel<Model, 256, kResume>), dim3(blocks), dim3(256), 0, stream, a);
     return hipGetLastError();
   }
 }
@@ -2790,39 +2770,40 @@ static hipError_t launch_shift_model(const SolveArgs& a, double* P, const double
   return hipGetLastError();
 }
 
+#ifdef MPCX_STAMPS
+// diagnostic build: this unit's setters of its own copies of the stamp/counter pointers
+static int diag_set_stamps(void* d) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_stamps), &d, sizeof(void*)); }
+static int diag_set_counters(void* d) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_diag), &d, sizeof(void*)); }
+#endif
+
+// The unit's record for solver.hip's registry, from the model's type alone.  (Not constexpr: a constant
+// host object would be emitted into the device code as well, with its references to host functions.)
+template <class Model>
+static ModelOps model_ops_of(const char* name) {
+  static_assert(RestoOf<Model>::value || !WsStashOf<Model>::value, "the chain stash lies after the restoration slots");
+  return ModelOps{name,
+                  Model::NX,
+                  Model::NU,
+                  RestoOf<Model>::value,
+                  WsStashOf<Model>::value,
+                  solve_shape<Model>,
+                  launch_solve_model<Model, false>,
+                  launch_solve_model<Model, true>,
+                  launch_plant_model<Model>,
+                  launch_constraints_model<Model>,
+                  launch_shift_model<Model>,
+#ifdef MPCX_STAMPS
+                  diag_set_stamps,
+                  diag_set_counters,
+#endif
+  };
+}
+
 }  // namespace mpcx
 
-// One translation unit per model: the launch entry points solver.hip dispatches to (and, in
-// the diagnostic build, this unit's setters of its own copies of the stamp/counter pointers).
-#ifdef MPCX_STAMPS
-#define MPCX_INSTANTIATE_DIAG(tag)                                                      \
-  int diag_set_stamps_##tag(void* d) {                                                  \
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_stamps), &d, sizeof(void*));        \
-  }                                                                                     \
-  int diag_set_counters_##tag(void* d) {                                                \
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_diag), &d, sizeof(void*));          \
-  }
-#else
-#define MPCX_INSTANTIATE_DIAG(tag)
-#endif
-#define MPCX_INSTANTIATE(Model, tag, name)                                                                  \
-  namespace mpcx {                                                                                          \
-  hipError_t solve_shape_##tag(const SolveArgs& a, int* G, int* R, const char** kname) {                     \
-    solve_shape<Model>(a, G, R);                                                                            \
-    *kname = name;                                                                                          \
-    return hipSuccess;                                                                                      \
-  }                                                                                                         \
-  hipError_t launch_solve_##tag(const SolveArgs& a, hipStream_t s) { return launch_solve_model<Model>(a, s); } \
-  hipError_t launch_resume_##tag(const SolveArgs& a, hipStream_t s) { return launch_resume_model<Model>(a, s); } \
-  hipError_t launch_plant_##tag(const SolveArgs& a, const double* U, double* XF, double* QF, hipStream_t s) {   \
-    return launch_plant_model<Model>(a, U, XF, QF, s);                                                      \
-  }                                                                                                         \
-  hipError_t launch_constraints_##tag(const SolveArgs& a, const double* W, double* Gout, hipStream_t s) {      \
-    return launch_constraints_model<Model>(a, W, Gout, s);                                                  \
-  }                                                                                                         \
-  hipError_t launch_shift_##tag(const SolveArgs& a, double* P, const double* W, double* W0, const double* L,  \
-                                double* L0, const double* LX, double* LX0, hipStream_t s) {                 \
-    return launch_shift_model<Model>(a, P, W, W0, L, L0, LX, LX0, s);                                       \
-  }                                                                                                         \
-  MPCX_INSTANTIATE_DIAG(tag)                                                                                \
+// One translation unit per model: it defines the record solver.hip's registry lists.
+#define MPCX_INSTANTIATE(Model, tag, name) \
+  namespace mpcx {                         \
+  extern const ModelOps ops_##tag;         \
+  const ModelOps ops_##tag = model_ops_of<Model>(name); \
   }

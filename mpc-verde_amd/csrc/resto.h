@@ -8,7 +8,7 @@
 // doubled -- and as an out-of-line call it still cost 20-30 % (the call ABI takes the AGPRs the
 // loop spills into).  So the solve launch only parks an instance whose line search fails: its
 // iterate, Newton step and loop scalars go to the workspace (RestoWs).  A second launch of the
-// same kernel (RESUME, launch_resume: a no-op for everything else) calls recover() on them and
+// same kernel (RESUME, ModelOps::resume: a no-op for everything else) calls recover() on them and
 // continues their solves, with recover() inlined there.
 //
 // What recover() does for a lane group whose line search failed (or that is in IPOPT's soft

@@ -139,24 +139,46 @@ struct RestoWs {
 __host__ __device__ constexpr int chain_ws_slots(int nx, int nu) {
   return (nx + nu) * (nx + nu + 1) / 2 + nx + nu + nx * nx + nx * nu + (nx + 1) * nx + 5 * (nx + nu) + nx;
 }
-// doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
-int resto_ws_slots(int model, int nx, int nu);
 
-hipError_t launch_solve(const SolveArgs& a, hipStream_t stream);
-// the solve kernel a launch with these arguments runs: G lanes per group, R replicas of the group per
-// wave, and the instantiation's model type ("mpcx::UnicycleFreeModel", ...)
-hipError_t solve_shape(const SolveArgs& a, int* G, int* R, const char** kname);
-// the resume launch of models with a restoration phase: continues the instances the solve
-// launch left at a failed line search (no-op for the others)
-hipError_t launch_resume(const SolveArgs& a, hipStream_t stream);
+// One solve unit (solve_<model>.hip): what the host needs to know about its stage model and the
+// launches of its kernels, all filled in from the model's type (kernels.h model_ops_of).
+struct ModelOps {
+  const char* name;      // the instantiation's model type ("mpcx::UnicycleFreeModel", ...)
+  int nx, nu;            // Model::NX, Model::NU
+  bool resto, ws_stash;  // RestoOf<Model>, WsStashOf<Model>: what the kernel keeps in SolveArgs::ws
+  // the solve kernel a launch with these arguments runs: G lanes per group, R replicas of the group per wave
+  void (*solve_shape)(const SolveArgs& a, int* G, int* R);
+  hipError_t (*solve)(const SolveArgs& a, hipStream_t stream);
+  // the resume launch of models with a restoration phase: continues the instances the solve
+  // launch left at a failed line search (no-op for the others)
+  hipError_t (*resume)(const SolveArgs& a, hipStream_t stream);
+  // plant: x+ = F(x0, u) for B instances (stage-0 model of each instance)
+  hipError_t (*plant)(const SolveArgs& a, const double* U, double* XF, double* QF, hipStream_t stream);
+  // constraint values g (B x ng) at w
+  hipError_t (*constraints)(const SolveArgs& a, const double* W, double* Gout, hipStream_t stream);
+  // closed-loop shift (plant + shifted warm start of primal and multipliers)
+  hipError_t (*shift)(const SolveArgs& a, double* P, const double* W, double* W0, const double* L, double* L0,
+                      const double* LX, double* LX0, hipStream_t stream);
+#ifdef MPCX_STAMPS
+  int (*set_stamps)(void* d_buf);  // diagnostic build: the unit's own copies of the buffer pointers
+  int (*set_counters)(void* d_buf);
+#endif
+  // doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
+  int ws_slots() const { return !resto ? 0 : RestoWs::slots(nx, nu) + (ws_stash ? chain_ws_slots(nx, nu) : 0); }
+};
+
+// One stage model of the registry (solver.hip): a value of mpcx_model and its solve units.
+struct ModelInfo {
+  int id;
+  bool ode;              // a nonlinear ODE model (ode.h)
+  bool fixed_dims;       // (nx, nu) are the model's (units[0]); otherwise the spec's pick the unit
+  const ModelOps* units[3];
+};
+const ModelInfo* model_info(int model);          // null: unknown model
+// the unit that solves these arguments (model, nx, nu, N, xbnd), or null when none fits
+const ModelOps* model_ops(const SolveArgs& a);
+
 hipError_t launch_rk4_sens(int B, int N, const StageParams& sp, const double* X, const double* U, const double* XR,
                            double* J, hipStream_t stream);
-// plant: x+ = F(x0, u) for B instances (stage-0 model of each instance)
-hipError_t launch_plant(const SolveArgs& a, const double* U, double* XF, double* QF, hipStream_t stream);
-// closed-loop shift (plant + shifted warm start of primal and multipliers)
-// constraint values g (B x ng) at w
-hipError_t launch_constraints(const SolveArgs& a, const double* W, double* Gout, hipStream_t stream);
-hipError_t launch_shift(const SolveArgs& a, double* P, const double* W, double* W0, const double* L, double* L0,
-                        const double* LX, double* LX0, hipStream_t stream);
 
 }  // namespace mpcx

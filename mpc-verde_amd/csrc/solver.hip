@@ -1,4 +1,4 @@
-// solver.hip -- model dispatch of the fused solve (kernels.h, one translation unit per model:
+// solver.hip -- model registry of the fused solve (kernels.h, one translation unit per model:
 // solve_<model>.hip) and the RK4+Jacobian sweep kernel over B x N unicycle intervals.
 //
 // Replaces, for B independent instances at once, the reference's
@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "mpcx.h"
 #include "solver.h"
 #include "unicycle.h"
 
@@ -88,34 +89,27 @@ hipError_t launch_rk4_sens(int B, int N, const StageParams& sp, const double* X,
   return hipGetLastError();
 }
 
-// workspace per thread: restoration (kernels.h RestoWs) for the unicycle and the ODE models, plus
-// the chain stash of the 6-state bicycle; none elsewhere
-int resto_ws_slots(int model, int nx, int nu) {
-  if (model != 1 && (model < 3 || model > 5) && model != 7) return 0;  // the models with kResto: unicycle (1), ODE (3-5, 7)
-  return RestoWs::slots(nx, nu) + (model == 4 ? chain_ws_slots(nx, nu) : 0);  // model 4: OdeModel<DynBicycle>::kWsStash
-}
+// ---- model registry: every stage model and its solve units (solve_<model>.hip) -------
+extern const ModelOps ops_unicycle, ops_unicycle_xfree, ops_unicycle_scan, ops_linear4, ops_linear5, ops_linear4x2,
+    ops_kin_bicycle, ops_dyn_bicycle, ops_cartpole, ops_path_bicycle;
 
-// ---- model dispatch (the entry points live in solve_<model>.hip) -------------------
-#define MPCX_DECLARE(tag)                                                                                       \
-  hipError_t launch_solve_##tag(const SolveArgs&, hipStream_t);                                                 \
-  hipError_t launch_resume_##tag(const SolveArgs&, hipStream_t);                                                \
-  hipError_t solve_shape_##tag(const SolveArgs&, int*, int*, const char**);                                     \
-  hipError_t launch_plant_##tag(const SolveArgs&, const double*, double*, double*, hipStream_t);                \
-  hipError_t launch_constraints_##tag(const SolveArgs&, const double*, double*, hipStream_t);                    \
-  hipError_t launch_shift_##tag(const SolveArgs&, double*, const double*, double*, const double*, double*,       \
-                                const double*, double*, hipStream_t);                                           \
-  int diag_set_stamps_##tag(void*);                                                                             \
-  int diag_set_counters_##tag(void*);
-MPCX_DECLARE(unicycle)
-MPCX_DECLARE(unicycle_xfree)
-MPCX_DECLARE(unicycle_scan)
-MPCX_DECLARE(linear4)
-MPCX_DECLARE(linear5)
-MPCX_DECLARE(linear4x2)
-MPCX_DECLARE(kin_bicycle)
-MPCX_DECLARE(dyn_bicycle)
-MPCX_DECLARE(cartpole)
-MPCX_DECLARE(path_bicycle)
+// unicycle, the linear-model shapes the reference's QPs need (4x1 lateral / cart-pole, 5x1
+// cart-pole with the previous input as a state; 4x2 for two-input models), and the BASELINE's nonlinear ODE variants
+static const ModelInfo kModels[] = {
+    // id, ODE model, (nx, nu) fixed by the model, solve units
+    {MPCX_MODEL_UNICYCLE, false, true, {&ops_unicycle_scan, &ops_unicycle, &ops_unicycle_xfree}},
+    {MPCX_MODEL_LINEAR, false, false, {&ops_linear4, &ops_linear5, &ops_linear4x2}},
+    {MPCX_MODEL_KIN_BICYCLE, true, true, {&ops_kin_bicycle}},
+    {MPCX_MODEL_DYN_BICYCLE, true, true, {&ops_dyn_bicycle}},
+    {MPCX_MODEL_CARTPOLE, true, true, {&ops_cartpole}},
+    {MPCX_MODEL_PATH_BICYCLE, true, true, {&ops_path_bicycle}},
+};
+
+const ModelInfo* model_info(int model) {
+  for (const ModelInfo& m : kModels)
+    if (m.id == model) return &m;
+  return nullptr;
+}
 
 // horizons from which the unicycle's Riccati recursion runs as a log-depth scan (models.h
 // UnicycleScanModel): ceil(log2(N+1)) = 5 combine levels cost about as much as 25 chain steps
@@ -133,53 +127,28 @@ static int unicycle_scan_min_n() {
   return n;
 }
 
-// unicycle, the linear-model shapes the reference's QPs need (4x1 lateral / cart-pole, 5x1
-// cart-pole with the previous input as a state; 4x2 for two-input models), and the BASELINE's nonlinear ODE variants
-#define MPCX_DISPATCH(a, FN, ...)                                                 \
-  do {                                                                            \
-    if ((a).model == 1)                                                           \
-      return (a).N >= unicycle_scan_min_n() ? FN##_unicycle_scan(__VA_ARGS__)                              \
-             : (a).xbnd ? FN##_unicycle(__VA_ARGS__) : FN##_unicycle_xfree(__VA_ARGS__);                       \
-    if ((a).model == 2 && (a).nx == 4 && (a).nu == 1) return FN##_linear4(__VA_ARGS__); \
-    if ((a).model == 2 && (a).nx == 5 && (a).nu == 1) return FN##_linear5(__VA_ARGS__); \
-    if ((a).model == 2 && (a).nx == 4 && (a).nu == 2) return FN##_linear4x2(__VA_ARGS__); \
-    if ((a).model == 3) return FN##_kin_bicycle(__VA_ARGS__);                     \
-    if ((a).model == 4) return FN##_dyn_bicycle(__VA_ARGS__);                     \
-    if ((a).model == 5) return FN##_cartpole(__VA_ARGS__);                        \
-    if ((a).model == 7) return FN##_path_bicycle(__VA_ARGS__);                    \
-    return hipErrorInvalidValue;                                                  \
-  } while (0)
-
-hipError_t launch_solve(const SolveArgs& a, hipStream_t stream) { MPCX_DISPATCH(a, launch_solve, a, stream); }
-hipError_t launch_resume(const SolveArgs& a, hipStream_t stream) { MPCX_DISPATCH(a, launch_resume, a, stream); }
-hipError_t solve_shape(const SolveArgs& a, int* G, int* R, const char** kname) {
-  MPCX_DISPATCH(a, solve_shape, a, G, R, kname);
-}
-hipError_t launch_plant(const SolveArgs& a, const double* U, double* XF, double* QF, hipStream_t stream) {
-  MPCX_DISPATCH(a, launch_plant, a, U, XF, QF, stream);
-}
-hipError_t launch_constraints(const SolveArgs& a, const double* W, double* Gout, hipStream_t stream) {
-  MPCX_DISPATCH(a, launch_constraints, a, W, Gout, stream);
-}
-hipError_t launch_shift(const SolveArgs& a, double* P, const double* W, double* W0, const double* L, double* L0,
-                        const double* LX, double* LX0, hipStream_t stream) {
-  MPCX_DISPATCH(a, launch_shift, a, P, W, W0, L, L0, LX, LX0, stream);
+const ModelOps* model_ops(const SolveArgs& a) {
+  const ModelInfo* m = model_info(a.model);
+  if (!m) return nullptr;
+  if (m->id == MPCX_MODEL_UNICYCLE)  // the row's units: scan, state-bounded, free states
+    return m->units[a.N >= unicycle_scan_min_n() ? 0 : a.xbnd ? 1 : 2];
+  if (m->fixed_dims) return m->units[0];
+  for (const ModelOps* u : m->units)
+    if (u && u->nx == a.nx && u->nu == a.nu) return u;
+  return nullptr;
 }
 
 }  // namespace mpcx
 
 #ifdef MPCX_STAMPS
 // diagnostic build: every model unit holds its own copy of the buffer pointers
-extern "C" int mpcx_diag_set_stamp_buffer(void* d_buf) {
-  using namespace mpcx;
-  return diag_set_stamps_unicycle(d_buf) | diag_set_stamps_unicycle_xfree(d_buf) | diag_set_stamps_unicycle_scan(d_buf) | diag_set_stamps_linear4(d_buf) | diag_set_stamps_linear5(d_buf) | diag_set_stamps_linear4x2(d_buf) |
-         diag_set_stamps_kin_bicycle(d_buf) | diag_set_stamps_dyn_bicycle(d_buf) | diag_set_stamps_cartpole(d_buf) |
-         diag_set_stamps_path_bicycle(d_buf);
+static int diag_set(int (*mpcx::ModelOps::*setter)(void*), void* d_buf) {
+  int r = 0;
+  for (const mpcx::ModelInfo& m : mpcx::kModels)
+    for (const mpcx::ModelOps* u : m.units)
+      if (u) r |= (u->*setter)(d_buf);
+  return r;
 }
-extern "C" int mpcx_diag_set_counter_buffer(void* d_buf) {
-  using namespace mpcx;
-  return diag_set_counters_unicycle(d_buf) | diag_set_counters_unicycle_xfree(d_buf) | diag_set_counters_unicycle_scan(d_buf) | diag_set_counters_linear4(d_buf) | diag_set_counters_linear5(d_buf) | diag_set_counters_linear4x2(d_buf) |
-         diag_set_counters_kin_bicycle(d_buf) | diag_set_counters_dyn_bicycle(d_buf) | diag_set_counters_cartpole(d_buf) |
-         diag_set_counters_path_bicycle(d_buf);
-}
+extern "C" int mpcx_diag_set_stamp_buffer(void* d_buf) { return diag_set(&mpcx::ModelOps::set_stamps, d_buf); }
+extern "C" int mpcx_diag_set_counter_buffer(void* d_buf) { return diag_set(&mpcx::ModelOps::set_counters, d_buf); }
 #endif

@@ -5,6 +5,7 @@ this module raises immediately -- there is no CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -13,12 +14,19 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPCX_LIB", os.path.join(_HERE, "libmpcx.so"))
 
-MODEL_UNICYCLE = 1
-MODEL_LINEAR = 2
-MODEL_KIN_BICYCLE = 3
-MODEL_DYN_BICYCLE = 4
-MODEL_CARTPOLE = 5
-MODEL_PATH_BICYCLE = 7  # 6 is unassigned (include/mpcx.h)
+Model = collections.namedtuple("Model", "id nx nu ode")
+# The stage models by name: the value of mpcx_model (include/mpcx.h; 6 is unassigned), the dimensions the
+# model fixes (the linear model takes them from its tables) and whether it is a nonlinear ODE model.
+# ocp.MODEL_IDS and ode.MODELS are views of this table.
+MODEL_TABLE = {"unicycle": Model(1, 3, 2, False), "linear": Model(2, None, None, False),
+               "kin_bicycle": Model(3, 3, 2, True), "dyn_bicycle": Model(4, 6, 2, True),
+               "cartpole": Model(5, 4, 1, True), "path_bicycle": Model(7, 4, 2, True)}
+MODEL_UNICYCLE = MODEL_TABLE["unicycle"].id
+MODEL_LINEAR = MODEL_TABLE["linear"].id
+MODEL_KIN_BICYCLE = MODEL_TABLE["kin_bicycle"].id
+MODEL_DYN_BICYCLE = MODEL_TABLE["dyn_bicycle"].id
+MODEL_CARTPOLE = MODEL_TABLE["cartpole"].id
+MODEL_PATH_BICYCLE = MODEL_TABLE["path_bicycle"].id
 COST_QUADRATURE = 0
 COST_NODE = 1
 P_X0_XREF = 0

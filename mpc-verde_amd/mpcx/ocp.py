@@ -99,9 +99,7 @@ def circular_reference(tau0, t, N, Delta=0.2):
     return np.stack([np.cos(0.1 * tau), np.sin(0.1 * tau), np.pi / 2 + 0.1 * tau, one, one], axis=-1)
 
 
-MODEL_IDS = {"unicycle": _lib.MODEL_UNICYCLE, "linear": _lib.MODEL_LINEAR, "kin_bicycle": _lib.MODEL_KIN_BICYCLE,
-             "dyn_bicycle": _lib.MODEL_DYN_BICYCLE, "cartpole": _lib.MODEL_CARTPOLE,
-             "path_bicycle": _lib.MODEL_PATH_BICYCLE}
+MODEL_IDS = {name: m.id for name, m in _lib.MODEL_TABLE.items()}
 
 
 # IPOPT termination / recovery options the spec carries (IPOPT's names); values left out take

@@ -34,8 +34,7 @@ import numpy as np
 
 from . import _lib
 
-MODELS = {"kin_bicycle": (_lib.MODEL_KIN_BICYCLE, 3, 2), "dyn_bicycle": (_lib.MODEL_DYN_BICYCLE, 6, 2),
-          "cartpole": (_lib.MODEL_CARTPOLE, 4, 1), "path_bicycle": (_lib.MODEL_PATH_BICYCLE, 4, 2)}
+MODELS = {name: (m.id, m.nx, m.nu) for name, m in _lib.MODEL_TABLE.items() if m.ode}  # (id, nx, nu)
 DYN_BICYCLE_PAR = (1200.0, 1.5, 2.0, 55000.0, 1350.0)  # m, a, b, Ca, Jz
 CARTPOLE_PAR = (1.0, 1.0, 0.5, 9.81, 10.0)              # M, m, L, g, c
 

@@ -412,6 +412,42 @@ def test_launch_shape_names_the_kernel(mpcx):
                                              "(mpcx::SolveArgs)")
 
 
+def test_every_model_reaches_its_solve_unit(mpcx):
+    """The model registry (csrc/solver.hip) picks, for each kind of handle, the solve unit built for it:
+    the ten instantiations' model types as csrc/solve_<model>.hip name them.  No solve is launched."""
+    import ctypes
+
+    L = mpcx._lib
+    lib = L.load()
+
+    def handle(model, N=10, nx=0, nu=0, bound_x=False):
+        s = L.Spec()
+        L.check(lib.mpcx_default_spec(ctypes.byref(s), L.MODEL_UNICYCLE if model == L.MODEL_LINEAR else model, N))
+        if model == L.MODEL_LINEAR:
+            s.model, s.nx, s.nu, s.cost, s.param_layout = model, nx, nu, L.COST_NODE, L.P_X0_STAGEREF
+            for i in range(8):
+                s.lbu[i], s.ubu[i], s.lbx[i], s.ubx[i] = -1.0, 1.0, -1e20, 1e20
+        if bound_x:
+            s.lbx[0], s.ubx[0] = -20.0, 20.0
+        return L.Handle(s)
+
+    units = [(handle(L.MODEL_UNICYCLE, bound_x=True), "mpcx::UnicycleModel"),
+             (handle(L.MODEL_UNICYCLE), "mpcx::UnicycleFreeModel"),
+             (handle(L.MODEL_UNICYCLE, N=30), "mpcx::UnicycleScanModel"),
+             (handle(L.MODEL_LINEAR, nx=4, nu=1), "mpcx::LinearModel<4, 1>"),
+             (handle(L.MODEL_LINEAR, nx=5, nu=1), "mpcx::LinearModel<5, 1>"),
+             (handle(L.MODEL_LINEAR, nx=4, nu=2), "mpcx::LinearModel<4, 2>"),
+             (handle(L.MODEL_KIN_BICYCLE), "mpcx::OdeModel<mpcx::KinBicycle>"),
+             (handle(L.MODEL_DYN_BICYCLE), "mpcx::OdeModel<mpcx::DynBicycle>"),
+             (handle(L.MODEL_CARTPOLE), "mpcx::OdeModel<mpcx::CartPole>"),
+             (handle(L.MODEL_PATH_BICYCLE), "mpcx::OdeModel<mpcx::PathBicycle>")]
+    for h, name in units:
+        assert f"mpcx::solve_kernel<{name}, " in h.launch_shape(16)[2], name
+        h.close()
+    with pytest.raises(L.MpcxError, match=r"linear model: \(nx, nu\) must be \(4, 1\), \(5, 1\) or \(4, 2\)"):
+        handle(L.MODEL_LINEAR, nx=3, nu=1)
+
+
 def test_instance_bits_do_not_depend_on_the_batch(mpcx):
     """SURVEY.md §4 item 5 at the group-variant boundary: the same config-2 instances solved in a
     batch of n_simd (1024 on MI355X: replicated 32-lane groups), inside a batch of 2 n_simd (narrow

@@ -88,6 +88,30 @@ def test_default_spec_without_gpu(lib):
         assert list(s.par[:len(par)]) == par
 
 
+def test_model_tables_agree(lib):
+    """The library's model registry (csrc/solver.hip), the header's enum and the Python table
+    (mpcx/_lib.py MODEL_TABLE) name the same models with the same dimensions; 6 (unassigned) and
+    8 (past the enum) are unknown."""
+    import mpcx
+
+    table = mpcx._lib.MODEL_TABLE
+    lib.mpcx_last_error.restype = ctypes.c_char_p
+    s = mpcx._lib.Spec()
+    for name, m in table.items():
+        if name == "linear":  # (nx, nu) come from the spec; no default spec
+            continue
+        assert lib.mpcx_default_spec(ctypes.byref(s), m.id, 20) == 0, name
+        assert (s.model, s.nx, s.nu) == (m.id, m.nx, m.nu), name
+    for model in (6, 8):
+        assert lib.mpcx_default_spec(ctypes.byref(s), model, 20) == -1  # MPCX_EINVAL
+        assert "unknown model" in lib.mpcx_last_error().decode()
+    enum = dict(re.findall(r"\b(MPCX_MODEL_\w+)\s*=\s*(\d+)", open(HDR).read()))
+    assert len(enum) >= 6
+    assert {"MPCX_MODEL_" + name.upper(): str(m.id) for name, m in table.items()} == enum
+    assert mpcx.ocp.MODEL_IDS == {name: m.id for name, m in table.items()}
+    assert mpcx.ode.MODELS == {name: (m.id, m.nx, m.nu) for name, m in table.items() if m.ode}
+
+
 def test_no_cpu_fallback_when_gpu_missing():
     """The product path fails loudly without a HIP device (no silent CPU path)."""
     import torch
