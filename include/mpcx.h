@@ -188,6 +188,29 @@ int mpcx_set_linear_model(mpcx_handle* h, int32_t n_tab, const double* A, const 
  * schedule given to mpcx_set_linear_model (which also clears this one). */
 int mpcx_set_linear_tab_dev(mpcx_handle* h, const int32_t* d_tab, int32_t tab_rows);
 
+/* Device-resident box bounds per instance (fleets with different actuator limits, per-vehicle
+ * corridors).  d_lbw and d_ubw are caller-owned device arrays n_steps x rows x n_w in the
+ * interleaved w layout, +-1e20 = no bound; rows = 1 (one row shared by the batch) or >= the batch
+ * size of every later launch (row b = instance b; a launch with more instances than rows returns
+ * MPCX_EINVAL and launches nothing).  The X_0 entries (index < nx) are never read.
+ * Precedence at a launch: the lbw / ubw arguments of mpcx_solve_batch, then the bounds installed
+ * here, then the spec's.  n_steps = 1 gives the same bounds at every closed-loop step.  With
+ * n_steps > 1 the array holds one block per step (a corridor that moves with time):
+ * mpcx_solve_batch_dev, mpcx_step_dev and mpcx_solve_batch read block 0, and a lock-step loop
+ * installs each step's block before the step (the setter on d_lbw + s rows n_w, n_steps = 1).
+ * mpcx_run_dev loads an instance's bounds once, at the start of the launch, and returns
+ * MPCX_EINVAL while bounds with n_steps > 1 are installed: reloading them at every step boundary
+ * inside the kernel cost the 20-step unicycle launch 7 % (profiles/instance_bounds/).
+ * Lifetime: the arrays must stay valid and unchanged while installed; after changing their
+ * contents call the setter again (it validates them and decides which kernel variant a launch
+ * runs).  Both pointers NULL reverts to the spec bounds; exactly one NULL is MPCX_EINVAL.
+ * Validation runs on the device, on `stream`: NaN, lb > ub, or lb == ub finite (a fixed
+ * variable) at an index >= nx returns MPCX_EINVAL, the message naming step, row and index of
+ * the first such entry, and leaves the handle's bounds as they were.  The call reads the result
+ * back, so it waits for `stream` and cannot be captured in a graph. */
+int mpcx_set_bounds_dev(mpcx_handle* h, const double* d_lbw, const double* d_ubw, int32_t rows, int32_t n_steps,
+                        void* stream);
+
 /* n_w, n_g, n_p of the NLP described by the handle. */
 int mpcx_dims(const mpcx_handle* h, int32_t* n_w, int32_t* n_g, int32_t* n_p);
 

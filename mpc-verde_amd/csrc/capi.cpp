@@ -48,6 +48,11 @@ struct mpcx_handle {
   double pc_epoch = 0, pc_gen = 1;
   double park_epoch = 0;  // solve launches with a restoration workspace (SolveArgs::park_flag)
   int spec_xbnd = 1;      // the spec bounds bound some state (SolveArgs::xbnd)
+  // caller-owned device bounds (mpcx_set_bounds_dev): steps x rows x nw each, or null (spec bounds)
+  const double *ext_lbw = nullptr, *ext_ubw = nullptr;
+  int ext_brows = 0, ext_bsteps = 0;
+  int ext_xbnd = 0;                          // some row bounds a state of a node >= 1 (the validation pass)
+  unsigned long long* d_bcheck = nullptr;    // the validation pass's two result words
 };
 
 namespace {
@@ -401,6 +406,7 @@ int mpcx_create(const mpcx_spec* s, mpcx_handle** out) {
       hipMalloc(&h->d_ubw, h->nw * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->d_lbw_call, h->nw * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->d_ubw_call, h->nw * sizeof(double)) != hipSuccess ||
+      hipMalloc(&h->d_bcheck, 2 * sizeof(unsigned long long)) != hipSuccess ||
       hipMemcpy(h->d_lbw, lb.data(), h->nw * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->d_ubw, ub.data(), h->nw * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
     mpcx_destroy(h);
@@ -418,6 +424,7 @@ void mpcx_destroy(mpcx_handle* h) {
   dev_free(h->d_ubw);
   dev_free(h->d_lbw_call);
   dev_free(h->d_ubw_call);
+  dev_free(h->d_bcheck);
   free_workspace(h);
   dev_free(h->d_sweep);
   dev_free(h->d_ws);
@@ -497,6 +504,50 @@ int mpcx_set_linear_tab_dev(mpcx_handle* h, const int32_t* d_tab, int32_t tab_ro
   return 0;
 }
 
+int mpcx_set_bounds_dev(mpcx_handle* h, const double* d_lbw, const double* d_ubw, int32_t rows, int32_t n_steps,
+                        void* stream) {
+  if (!h) return fail(MPCX_EINVAL, "null handle");
+  if (!d_lbw && !d_ubw) {  // back to the spec bounds
+    h->ext_lbw = h->ext_ubw = nullptr;
+    h->ext_brows = h->ext_bsteps = h->ext_xbnd = 0;
+    h->pc_gen += 1;
+    return 0;
+  }
+  if (!d_lbw || !d_ubw) return fail(MPCX_EINVAL, "mpcx_set_bounds_dev: d_lbw and d_ubw must both be given (or both NULL)");
+  if (rows < 1) return fail(MPCX_EINVAL, "mpcx_set_bounds_dev: rows must be >= 1");
+  if (n_steps < 1) return fail(MPCX_EINVAL, "mpcx_set_bounds_dev: n_steps must be >= 1");
+  DEVICE_SCOPE(h->spec.device);
+  hipStream_t s = (hipStream_t)stream;
+  // validation on the device; the two result words are read back, so the call waits for `stream`
+  unsigned long long res[2] = {mpcx::kBoundsOk, 0};
+  const long n = (long)n_steps * rows * h->nw;
+  HIPCHK(hipMemcpyAsync(h->d_bcheck, res, sizeof res, hipMemcpyHostToDevice, s));
+  HIPCHK(mpcx::launch_check_bounds(d_lbw, d_ubw, n, h->nw, h->spec.nx, h->spec.nu, h->d_bcheck, s));
+  HIPCHK(hipMemcpyAsync(res, h->d_bcheck, sizeof res, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (res[0] != mpcx::kBoundsOk) {  // the installed bounds (if any) stay as they were
+    const long j = (long)(res[0] >> 2), per_step = (long)rows * h->nw;
+    const std::string where = "step " + std::to_string(j / per_step) + ", row " + std::to_string(j % per_step / h->nw) +
+                              ", index " + std::to_string(j % h->nw);
+    return fail(MPCX_EINVAL, (res[0] & 3) == 1 ? "lbw/ubw: NaN or lb > ub at " + where
+                                               : "lbw == ubw (fixed variable) is not supported, " + where);
+  }
+  h->ext_lbw = d_lbw;
+  h->ext_ubw = d_ubw;
+  h->ext_brows = rows;
+  h->ext_bsteps = n_steps;
+  h->ext_xbnd = res[1] != 0 ? 1 : 0;
+  h->pc_gen += 1;  // the decoupled suffix's start follows the bounds
+  return 0;
+}
+
+// installed device bounds: one row shared by the batch, or a row for every instance
+static int check_bound_rows(const mpcx_handle* h, int B) {
+  if (h->ext_lbw && h->ext_brows != 1 && B > h->ext_brows)
+    return fail(MPCX_EINVAL, "batch larger than the installed bound rows (mpcx_set_bounds_dev)");
+  return 0;
+}
+
 static int check_model_ready(const mpcx_handle* h, int B) {
   if (h->spec.model != MPCX_MODEL_LINEAR) return 0;
   if (!h->d_linA) return fail(MPCX_EINVAL, "linear model tables not set (mpcx_set_linear_model)");
@@ -558,9 +609,16 @@ static mpcx::SolveArgs make_args(const mpcx_handle* h, int B, const SolveIO& io)
   a.mu_init = h->spec.warm_mu_init;
   a.bound_push = h->spec.warm_bound_push;
   a.mult_push = h->spec.warm_mult_push;
-  a.lbw = h->d_lbw;  // the spec's bounds (mpcx_solve_batch: the call's)
-  a.ubw = h->d_ubw;
-  a.xbnd = h->spec_xbnd;
+  if (h->ext_lbw) {  // installed device bounds (mpcx_set_bounds_dev), block 0
+    a.lbw = h->ext_lbw;
+    a.ubw = h->ext_ubw;
+    a.bnd_row = h->ext_brows > 1 ? h->nw : 0;
+    a.xbnd = h->ext_xbnd;
+  } else {  // the spec's bounds (mpcx_solve_batch with lbw / ubw: the call's)
+    a.lbw = h->d_lbw;
+    a.ubw = h->d_ubw;
+    a.xbnd = h->spec_xbnd;
+  }
   a.w_out = io.w;
   a.f_out = io.f;
   a.lam_out = io.lam;
@@ -638,7 +696,9 @@ static int solve_launch(mpcx_handle* h, mpcx::SolveArgs& a, hipStream_t stream) 
   // decoupled-suffix value functions of earlier launches (kernels.h "decoupled suffix").  Not
   // with a caller-owned device schedule (mpcx_set_linear_tab_dev): the caller may rewrite it on
   // the device between launches without a call the cache's generation could follow.
-  if (a.model == MPCX_MODEL_LINEAR && h->lin_dec != 0 && h->ext_tab == nullptr) {
+  // Nor with per-instance bounds: the suffix starts where an instance's last bounded state
+  // ends, and the cache holds one suffix for the whole launch.
+  if (a.model == MPCX_MODEL_LINEAR && h->lin_dec != 0 && h->ext_tab == nullptr && a.bnd_row == 0) {
     if (!h->d_pcache) {
       const size_t n = (size_t)(a.N + 2) * (a.nx * (a.nx + 1) / 2);
       HIPCHK(hipMalloc(&h->d_pcache, n * sizeof(double)));
@@ -661,6 +721,7 @@ int mpcx_solve_batch_dev(mpcx_handle* h, int32_t B, const double* d_P, const dou
   if (B < 0) return fail(MPCX_EINVAL, "B < 0");
   if (B == 0) return 0;
   if (int r = check_model_ready(h, B)) return r;
+  if (int r = check_bound_rows(h, B)) return r;
   DEVICE_SCOPE(h->spec.device);
   mpcx::SolveArgs a = make_args(h, B, {.P = d_P, .w0 = d_w0, .lam0 = d_lam_g0, .lamx0 = d_lam_x0, .w = d_w_out,
                                        .f = d_f_out, .lam = d_lam_g, .lamx = d_lam_x, .status = d_status,
@@ -676,6 +737,7 @@ int mpcx_step_dev(mpcx_handle* h, int32_t B, double* d_P, double* d_w0, double* 
   if (flags & ~(MPCX_STEP_COLD | MPCX_STEP_PRIMAL_ONLY)) return fail(MPCX_EINVAL, "unknown flags");
   if (B == 0) return 0;
   if (int r = check_model_ready(h, B)) return r;
+  if (int r = check_bound_rows(h, B)) return r;
   DEVICE_SCOPE(h->spec.device);
   const bool cold = flags & MPCX_STEP_COLD;
   const bool duals = !cold && !(flags & MPCX_STEP_PRIMAL_ONLY);
@@ -695,6 +757,11 @@ int mpcx_run_dev(mpcx_handle* h, int32_t B, int32_t K, double* d_P, double* d_w0
   if (d_tabseq && h->spec.model != MPCX_MODEL_LINEAR) return fail(MPCX_EINVAL, "d_tabseq needs a linear model");
   if (B == 0) return 0;
   if (int r = check_model_ready(h, B)) return r;
+  if (int r = check_bound_rows(h, B)) return r;
+  // a multi-step launch loads an instance's bounds once, at its start
+  if (h->ext_lbw && h->ext_bsteps > 1)
+    return fail(MPCX_EINVAL, "mpcx_run_dev: per-step bounds (mpcx_set_bounds_dev with n_steps > 1) are not followed "
+                             "inside a multi-step launch; step with mpcx_step_dev and set each step's bounds before it");
   DEVICE_SCOPE(h->spec.device);
   const bool cold = flags & MPCX_STEP_COLD;
   const bool duals = !(flags & MPCX_STEP_PRIMAL_ONLY) && (d_lam_g0 || d_lam_x0);
@@ -716,12 +783,12 @@ int mpcx_solve_batch(mpcx_handle* h, int32_t B, const double* P, const double* w
   if (B == 0) return 0;
   if (int r = check_bounds_vec(h, lbw, ubw)) return r;
   if (int r = check_model_ready(h, B)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
   DEVICE_SCOPE(h->spec.device);
   if (int r = ensure(h, B)) return r;
   hipStream_t s = h->stream;
-  const double* dl = h->d_lbw;
-  const double* du = h->d_ubw;
-  int call_xbnd = h->spec_xbnd;
+  int call_xbnd = 0;
   if (lbw || ubw) {
     std::vector<double> lb, ub;
     spec_bounds(h->spec, lb, ub);
@@ -738,8 +805,6 @@ int mpcx_solve_batch(mpcx_handle* h, int32_t B, const double* P, const double* w
     HIPCHK(hipMemcpyAsync(h->d_lbw_call, lb.data(), h->nw * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->d_ubw_call, ub.data(), h->nw * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    dl = h->d_lbw_call;
-    du = h->d_ubw_call;
     call_xbnd = state_bounded(lb, ub, h->spec.nx, h->spec.nu, h->spec.N);
   }
   HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
@@ -750,9 +815,12 @@ int mpcx_solve_batch(mpcx_handle* h, int32_t B, const double* P, const double* w
                                        .lamx0 = lam_x0 ? h->d_lamx0 : nullptr, .w = h->d_w, .f = h->d_f,
                                        .lam = lam_g ? h->d_lam : nullptr, .lamx = lam_x ? h->d_lamx : nullptr,
                                        .status = h->d_status, .iters = h->d_iters});
-  a.lbw = dl;
-  a.ubw = du;
-  a.xbnd = call_xbnd;
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
   if (int r = solve_launch(h, a, s)) return r;
   if (lam_x) HIPCHK(hipMemcpyAsync(lam_x, h->d_lamx, (size_t)B * h->nw * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(w_out, h->d_w, (size_t)B * h->nw * sizeof(double), hipMemcpyDeviceToHost, s));

@@ -340,16 +340,25 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
     lb0[i] = -1e20;
     ub0[i] = 1e20;
   }
-  if (XBoundsOf<Model>::value && hasX && k > 0)
-    for (int i = 0; i < NX; ++i) {
-      lb0[i] = a.lbw[ixw<NX, NU>(k, i)];
-      ub0[i] = a.ubw[ixw<NX, NU>(k, i)];
-    }
-  if (hasU)
-    for (int i = 0; i < NU; ++i) {
-      lb0[NX + i] = a.lbw[iuw<NX, NU>(k, i)];
-      ub0[NX + i] = a.ubw[iuw<NX, NU>(k, i)];
-    }
+  {
+    // this instance's row of the bounds (mpcx_set_bounds_dev; stride 0: one row shared by the
+    // batch, and a lane past the batch reads row 0).  A group that fills its wave keeps the row
+    // scalar, so the loads address as the shared bounds' do (uniform base + the node's offset).
+    int row = valid ? inst : 0;
+    if constexpr (G * R >= 64) row = __builtin_amdgcn_readfirstlane(row);
+    const double* lbr = a.lbw + (size_t)row * a.bnd_row;
+    const double* ubr = a.ubw + (size_t)row * a.bnd_row;
+    if (XBoundsOf<Model>::value && hasX && k > 0)
+      for (int i = 0; i < NX; ++i) {
+        lb0[i] = lbr[ixw<NX, NU>(k, i)];
+        ub0[i] = ubr[ixw<NX, NU>(k, i)];
+      }
+    if (hasU)
+      for (int i = 0; i < NU; ++i) {
+        lb0[NX + i] = lbr[iuw<NX, NU>(k, i)];
+        ub0[NX + i] = ubr[iuw<NX, NU>(k, i)];
+      }
+  }
   int nbnd_l = 0;
   constexpr bool kXB = XBoundsOf<Model>::value;  // false: no state is bounded (compile-time)
 #pragma unroll
@@ -780,7 +789,8 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
           io.soft_count = soft_count;
           io.xslot = xw.slot;
           io.fovf = 0;
-          recover<Model, G>(io, filt, ma, ctx, wsl, wst, a.lbw, a.ubw, xch);
+          const size_t brow = (size_t)(valid ? inst : 0) * a.bnd_row;  // the instance's row, as at the solve's start
+          recover<Model, G>(io, filt, ma, ctx, wsl, wst, a.lbw + brow, a.ubw + brow, xch);
 #pragma unroll
           for (int i = 0; i < NZ; ++i) {
             z[i] = W(RestoWs::XZ + i);

@@ -155,7 +155,7 @@ struct RecIO {
 };
 
 template <class Model, int G>
-// (inlined into the resume launch, its only caller)
+// (inlined into the resume launch, its only caller; lbw / ubw: the instance's own row of the bounds)
 __device__ __forceinline__ void recover(RecIO& io, FilterLds<G>& filt, const ModelArgs ma, const typename Model::Ctx ctx,
                                         double* wsl, const long wst, const double* lbw, const double* ubw, double* xbuf) {
   constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NH = NZ * (NZ + 1) / 2, NP = NX * (NX + 1) / 2;

@@ -62,7 +62,7 @@ struct SolveArgs {
   const double* lamx0;  // B x nw initial bound multipliers (zU - zL) or null
   int warm;             // 1: IPOPT warm_start_init_point (multipliers given)
   double mu_init, bound_push, mult_push;
-  const double* lbw;    // nw (device)
+  const double* lbw;    // nw (device), or one row of nw per instance (bnd_row below)
   const double* ubw;    // nw
   double* w_out;        // B x nw
   double* f_out;        // B or null
@@ -82,6 +82,11 @@ struct SolveArgs {
   int warm_next;         // steps >= 1 start from shifted multipliers (1) or primal only (0)
   const double* Pseq;    // steps x B x p_stride stage references per step (x0 part unused) or null
   const int32_t* tabseq; // steps x B x N linear-model schedule per step or null
+  // per-instance bounds (mpcx_set_bounds_dev): doubles between the rows of consecutive instances in
+  // lbw / ubw, 0 = one row for the batch.  Last, so that every other argument keeps its offset: the
+  // solve kernels run with every register allocated, and how the arguments pack into scalar loads
+  // shows in their spills.
+  long bnd_row;
 };
 
 // What a stage model reads (a local copy: taking the address of the kernel argument
@@ -177,6 +182,15 @@ struct ModelInfo {
 const ModelInfo* model_info(int model);          // null: unknown model
 // the unit that solves these arguments (model, nx, nu, N, xbnd), or null when none fits
 const ModelOps* model_ops(const SolveArgs& a);
+
+// Validation pass of caller-owned device bounds (mpcx_set_bounds_dev): n = steps x rows x nw entries
+// of lbw / ubw in the interleaved w layout.  res[0] receives the smallest key 4 j + kind over the
+// offending entries j (kind 1: NaN or lb > ub, 2: lb == ub finite; X_0's entries are not looked
+// at) and keeps kBoundsOk when there is none; res[1] becomes 1 when some state of a node >= 1 has
+// a finite bound in some row (SolveArgs::xbnd).  The caller sets res = {kBoundsOk, 0} beforehand.
+constexpr unsigned long long kBoundsOk = ~0ull;
+hipError_t launch_check_bounds(const double* lbw, const double* ubw, long n, int nw, int nx, int nu,
+                               unsigned long long* res, hipStream_t stream);
 
 hipError_t launch_rk4_sens(int B, int N, const StageParams& sp, const double* X, const double* U, const double* XR,
                            double* J, hipStream_t stream);

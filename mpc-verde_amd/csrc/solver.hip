@@ -89,6 +89,47 @@ hipError_t launch_rk4_sens(int B, int N, const StageParams& sp, const double* X,
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------
+// Validation of device-resident bounds (mpcx_set_bounds_dev): the checks the host makes on a
+// call's lbw / ubw (capi.cpp check_bounds_vec) and the state-bounded flag (state_bounded), over
+// steps x rows x nw entries.  Grid-stride loop, one wave reduction, then one atomic per wave and
+// result word; the first offender in array order is the smallest key.
+// ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void check_bounds_kernel(const double* __restrict__ lbw,
+                                                           const double* __restrict__ ubw, long n, int nw, int nx,
+                                                           int nu, unsigned long long* res) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  unsigned long long first = kBoundsOk;
+  int xb = 0;
+  for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+    const int i = (int)(j % nw);
+    if (i < nx) continue;  // X_0 is pinned by g_0: its bounds are never read
+    const double l = lbw[j], u = ubw[j];
+    const int kind = (l != l || u != u || l > u) ? 1 : (l == u && l > -1e19) ? 2 : 0;
+    const unsigned long long key = 4ull * (unsigned long long)j + (unsigned)kind;
+    if (kind != 0 && key < first) first = key;
+    const bool state = (i - nx) % (nx + nu) >= nu;  // z_k = (U_k, X_{k+1}): a state of node k + 1 >= 1
+    xb |= (state && (l > -1e19 || u < 1e19)) ? 1 : 0;
+  }
+  for (int o = warpSize / 2; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(first, o);
+    first = other < first ? other : first;
+    xb |= __shfl_xor(xb, o);
+  }
+  if ((threadIdx.x & (warpSize - 1)) == 0) {
+    if (first != kBoundsOk) atomicMin(&res[0], first);
+    if (xb) atomicOr(&res[1], 1ull);
+  }
+}
+
+hipError_t launch_check_bounds(const double* lbw, const double* ubw, long n, int nw, int nx, int nu,
+                               unsigned long long* res, hipStream_t stream) {
+  long blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(check_bounds_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, lbw, ubw, n, nw, nx, nu, res);
+  return hipGetLastError();
+}
+
 // ---- model registry: every stage model and its solve units (solve_<model>.hip) -------
 extern const ModelOps ops_unicycle, ops_unicycle_xfree, ops_unicycle_scan, ops_linear4, ops_linear5, ops_linear4x2,
     ops_kin_bicycle, ops_dyn_bicycle, ops_cartpole, ops_path_bicycle;

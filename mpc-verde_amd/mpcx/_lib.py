@@ -39,7 +39,7 @@ STATUS = {0: "Solve_Succeeded", 1: "Solved_To_Acceptable_Level", 2: "Maximum_Ite
 EXPORTS = ("mpcx_default_spec", "mpcx_create", "mpcx_destroy", "mpcx_last_error", "mpcx_dims", "mpcx_solve_batch",
            "mpcx_solve_batch_dev", "mpcx_plant_step", "mpcx_shift_dev", "mpcx_rk4_sens", "mpcx_rk4_sens_dev",
            "mpcx_set_linear_model", "mpcx_set_linear_tab_dev", "mpcx_step_dev", "mpcx_run_dev",
-           "mpcx_source_hash", "mpcx_launch_shape")
+           "mpcx_source_hash", "mpcx_launch_shape", "mpcx_set_bounds_dev")
 STEP_COLD = 1
 STEP_PRIMAL_ONLY = 2
 
@@ -144,6 +144,7 @@ def load():
     lib.mpcx_rk4_sens_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp]
     lib.mpcx_set_linear_model.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, ip, ctypes.c_int32]
     lib.mpcx_set_linear_tab_dev.argtypes = [H, ctypes.c_void_p, ctypes.c_int32]
+    lib.mpcx_set_bounds_dev.argtypes = [H, vp, vp, ctypes.c_int32, ctypes.c_int32, vp]
     lib.mpcx_step_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp]
     lib.mpcx_run_dev.argtypes = [H, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp,
                                  vp, vp, vp, vp]
@@ -213,6 +214,15 @@ class Handle:
         buf = ctypes.create_string_buffer(256)
         check(load().mpcx_launch_shape(self._h, int(B), ctypes.byref(G), ctypes.byref(R), buf, len(buf)))
         return G.value, R.value, buf.value.decode()
+
+    def set_bounds_dev(self, d_lbw, d_ubw, rows=1, n_steps=1, stream=None):
+        """Install caller-owned device bounds (mpcx_set_bounds_dev): d_lbw / d_ubw are device addresses
+        (int) of n_steps x rows x n_w float64 arrays that stay alive and unchanged while installed; both
+        None reverts to the spec bounds.  The call validates them on ``stream`` and waits for it."""
+        vp = ctypes.c_void_p
+        check(load().mpcx_set_bounds_dev(self._h, None if d_lbw is None else vp(d_lbw),
+                                         None if d_ubw is None else vp(d_ubw), int(rows), int(n_steps),
+                                         None if stream is None else vp(stream)))
 
     @property
     def spec(self):

@@ -129,6 +129,10 @@ class DeviceLoop:
         K = int(K)
         if K < 1:
             raise ValueError("K must be >= 1")
+        bnd = self.solver._dev_bounds
+        if bnd is not None and bnd[3] > 1:
+            raise ValueError(f"run: per-step bounds ({bnd[3]} steps) are installed and a multi-step launch loads an "
+                             "instance's bounds once, at its start; call step() with set_bounds() before each step")
         z = lambda: torch.zeros((K, self.B), dtype=torch.int32, device=self.device)  # noqa: E731
         st = z() if status_out is None else _check(status_out, "status_out", torch.int32, (K, self.B), self.device)
         it = z() if iters_out is None else _check(iters_out, "iters_out", torch.int32, (K, self.B), self.device)
@@ -160,6 +164,36 @@ class DeviceLoop:
         _check(tab, "tab", torch.int32, (self.B, self.solver.ocp.N), self.device)
         self._tab = tab
         _lib.check(lib.mpcx_set_linear_tab_dev(self.solver._h.ptr, ctypes_void(tab.data_ptr()), self.B))
+
+    def set_bounds(self, lbw, ubw):
+        """Per-instance box bounds of the next solves (mpcx_set_bounds_dev): lbw / ubw are float64
+        device tensors (B, n_w), one row per instance in the solver's w layout, +-1e20 = no bound
+        (the X_0 entries are not read); None, None reverts to the problem's bounds.  (K, B, n_w)
+        tensors hold K steps' bounds (a corridor that moves with time): solve() and step() read
+        block 0 and run() refuses them -- such a loop is stepped in lock step, set_bounds(lb[s],
+        ub[s]) before step s.  The tensors are validated on the loop's stream (the call waits for it; a NaN,
+        lb > ub or lb == ub raises and leaves the bounds as they were) and are kept alive here;
+        they must not be written to while installed -- call set_bounds again after changing them."""
+        if lbw is None and ubw is None:
+            self.solver._install_bounds(None)
+            return
+        if lbw is None or ubw is None:
+            raise ValueError("set_bounds: lbw and ubw must both be given (or both None)")
+        pd = getattr(self.solver, "_pad", None)
+        n_w = pd.n_w if pd is not None else self.solver._h.n_w
+        K = lbw.shape[0] if isinstance(lbw, torch.Tensor) and lbw.dim() == 3 else None
+        shape = (self.B, n_w) if K is None else (K, self.B, n_w)
+        _check(lbw, "lbw", torch.float64, shape, self.device)
+        _check(ubw, "ubw", torch.float64, shape, self.device)
+        if pd is not None:  # user layout -> the kernel's padded layout, pad states unbounded
+            idx = torch.from_numpy(pd.w_idx).to(self.device)
+            with torch.cuda.stream(self.stream):
+                full = [torch.full(shape[:-1] + (pd.n_w_pad,), inf, dtype=torch.float64, device=self.device)
+                        for inf in (-1e20, 1e20)]
+                full[0][..., idx] = lbw
+                full[1][..., idx] = ubw
+            lbw, ubw = full
+        self.solver._install_bounds((lbw, ubw, self.B, 1 if K is None else K), self.stream.cuda_stream)
 
     def step(self, status_out=None, iters_out=None):
         """One closed-loop step = ONE kernel launch (mpcx_step_dev): the batched solve and,

@@ -46,10 +46,34 @@ def _vec(v, n, name, fill=None):
     return np.ascontiguousarray(a)
 
 
+def _batch_bounds(lbw, ubw, B, nw):
+    """The lbw / ubw arguments of ``solve_batch``: (lbw, ubw, per_instance).  Scalars and n_w vectors
+    (rows and columns included) are one bound vector for the batch, as ever (None = the spec's);
+    a matrix is one row per instance and must be (B, n_w) -- then both are returned as (B, n_w)
+    arrays, a scalar or vector counterpart repeated for every instance.  Entries at or beyond
+    +-1e19 become +-1e20 (no bound); NaN is kept for the library to refuse."""
+    arrs = [None if v is None else np.asarray(v, dtype=np.float64) for v in (lbw, ubw)]
+    matrix = [a is not None and a.ndim >= 2 and (a.ndim > 2 or min(a.shape) > 1) for a in arrs]
+    if not any(matrix):
+        return _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw"), False
+    out = []
+    for a, m, name, inf in zip(arrs, matrix, ("lbw", "ubw"), (-1e20, 1e20)):
+        if a is None:
+            raise ValueError(f"{name}: per-instance bounds need both lbw and ubw")
+        if m and a.shape != (B, nw):
+            raise ValueError(f"{name}: expected ({B}, {nw}) per-instance bounds or {nw} entries, got {a.shape}")
+        if not m:
+            a = np.broadcast_to(_vec(a, nw, name), (B, nw))
+        keep = np.isnan(a) | (a > -1e19 if inf < 0 else a < 1e19)
+        out.append(np.ascontiguousarray(np.where(keep, a, inf)))
+    return out[0], out[1], True
+
+
 class Solver:
     """Callable returned by :func:`nlpsol`."""
 
     _pad = None  # lti.StatePad of a linear model embedded in a larger kernel instantiation
+    _dev_bounds = None  # installed device bounds: (lbw, ubw, rows, n_steps), the tensors kept alive
 
     def __init__(self, name: str, ocp: OCP, opts: dict | None = None, device: int = 0):
         opts = dict(opts or {})
@@ -78,6 +102,15 @@ class Solver:
         if ocp.model == "linear":
             self._h.set_linear_model(kocp)
         self._stats = {}
+
+    def _install_bounds(self, state, stream=None):
+        """mpcx_set_bounds_dev with device tensors (lbw, ubw, rows, n_steps), or None = the spec bounds."""
+        if state is None:
+            self._h.set_bounds_dev(None, None)
+        else:
+            lb, ub, rows, n_steps = state
+            self._h.set_bounds_dev(lb.data_ptr(), ub.data_ptr(), rows, n_steps, stream)
+        self._dev_bounds = state
 
     def set_linear_model(self, lin=None):
         """Re-upload stage tables (LTV: new tables or per-instance schedule for the next step)."""
@@ -125,6 +158,9 @@ class Solver:
         """Solve B independent NLPs (multiple-shooting layout).
 
         P (B, n_p); w0 (B, n_w) or None (cold start X_k = x0, U = 0);
+        lbw / ubw: None (the problem's bounds), a scalar or n_w entries shared by the batch, or
+        (B, n_w) arrays with one row per instance (uploaded and installed as device bounds for
+        this call, mpcx_set_bounds_dev, then whatever was installed before is put back);
         lam_g0 (B, n_g) / lam_x0 (B, n_w): warm-start multipliers (IPOPT
         warm_start_init_point), or None.
         Returns dict of arrays: w (B,n_w), f (B,), lam_g (B,n_g), lam_x (B,n_w), status (B,), iters (B,),
@@ -138,16 +174,18 @@ class Solver:
         w0a = None
         if w0 is not None:
             w0a = np.ascontiguousarray(np.asarray(w0, np.float64).reshape(B, nw))
-        lbw = _vec(lbw, nw, "lbw")  # the library reads n_w entries of each
-        ubw = _vec(ubw, nw, "ubw")
+        lbw, ubw, per_instance = _batch_bounds(lbw, ubw, B, nw)  # the library reads n_w entries of each row
         l0 = None if lam_g0 is None else np.ascontiguousarray(np.asarray(lam_g0, np.float64).reshape(B, ng))
         lx0 = None if lam_x0 is None else np.ascontiguousarray(np.asarray(lam_x0, np.float64).reshape(B, nw))
         pd = self._pad
         if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
             P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
             w0a = pd.scatter(w0a, pd.w_idx, pd.n_w_pad)
-            lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
-            ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
+            if per_instance:
+                lbw, ubw = pd.scatter(lbw, pd.w_idx, pd.n_w_pad, -1e20), pd.scatter(ubw, pd.w_idx, pd.n_w_pad, 1e20)
+            else:
+                lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
+                ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
             l0 = pd.scatter(l0, pd.g_idx, pd.n_g_pad)
             lx0 = pd.scatter(lx0, pd.w_idx, pd.n_w_pad)
             nw, ng = pd.n_w_pad, pd.n_g_pad
@@ -159,10 +197,23 @@ class Solver:
         st = np.empty(B, np.int32)
         it = np.empty(B, np.int32)
         lib = _lib.load()
+        before = self._dev_bounds
+        if per_instance:  # device memory comes from PyTorch, as in mpcx.device
+            import torch
+
+            dev = torch.device("cuda", self._h.spec.device)
+            self._install_bounds((torch.from_numpy(lbw).to(dev), torch.from_numpy(ubw).to(dev), B, 1),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+            lbw = ubw = None
         t0 = time.perf_counter()
-        _lib.check(lib.mpcx_solve_batch(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w0a), _lib.dptr(l0), _lib.dptr(lx0),
-                                        _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(w), _lib.dptr(f), _lib.dptr(g),
-                                        _lib.dptr(lam), _lib.dptr(lamx), _lib.iptr(st), _lib.iptr(it)))
+        try:
+            _lib.check(lib.mpcx_solve_batch(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w0a), _lib.dptr(l0),
+                                            _lib.dptr(lx0), _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(w), _lib.dptr(f),
+                                            _lib.dptr(g), _lib.dptr(lam), _lib.dptr(lamx), _lib.iptr(st),
+                                            _lib.iptr(it)))
+        finally:
+            if per_instance:  # (the solve has finished: mpcx_solve_batch waits for its results)
+                self._install_bounds(before)
         t = time.perf_counter() - t0
         if pd is not None:
             w, lamx = pd.gather(w, pd.w_idx), pd.gather(lamx, pd.w_idx)
