@@ -67,10 +67,15 @@ constexpr int kDiag = 15;  // counters per instance
 // finer split of the errors and Riccati phases (diagnostic build with -DMPCX_STAMP_SUB)
 #if defined(MPCX_STAMPS) && defined(MPCX_STAMP_SUB)
 #define STAMP_SUB(p) STAMP(p)
+// the stamp state, handed to the functions (backward.h) that stamp sub-phases inside themselves
+#define MPCX_STAMP_PARAMS , unsigned long long* st_acc, unsigned long long& st_last, int& st_ph
+#define MPCX_STAMP_ARGS , st_acc, st_last, st_ph
 #else
 #define STAMP_SUB(p) \
   do {               \
   } while (0)
+#define MPCX_STAMP_PARAMS
+#define MPCX_STAMP_ARGS
 #endif
 #ifndef MPCX_STAMPS
 #define DIAG(i) \
@@ -250,6 +255,10 @@ struct RowChainOf<M, std::void_t<decltype(M::kRowChain)>> {
   static constexpr bool value = M::kRowChain;
 };
 
+}  // namespace mpcx
+#include "backward.h"  // the backward Riccati sweeps, one function per strategy
+namespace mpcx {
+
 // R = 2 (replicated groups, G = 32): a batch too small to give every SIMD a wave runs one
 // instance per wave with its lane group held TWICE, in the wave's two 32-lane halves (replica rho
 // = lane / 32).  Both replicas compute the same bits (every collective is a 32-lane group
@@ -285,23 +294,11 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
   // the row chain's node records (rowchain.h): G records per instance of the wave
   constexpr bool kRow = RowChainOf<Model>::value && rowchain::fits<Model>() && G >= 32 && G * R <= 64;
   __shared__ double rcbuf[kRow ? (64 / (G * R)) * G * rowchain::kRec : 1];
-  // workspace chain stash (solver.h chain_ws_slots): slots after the restoration workspace's
+  // workspace chain stash (solver.h ChainRec): this thread's record, after the restoration
+  // workspace's slots (backward.h chain_record)
   constexpr bool kWsStash = WsStashOf<Model>::value;
-  // The stash is one contiguous record per thread (array of structures, after the restoration
-  // workspace's slot-major part): the chain's single active lane then reads its operands from
-  // a few cache lines in 16-byte loads instead of one line per value.
-  constexpr int kWsH = RestoWs::slots(NX, NU);  // slot-major slots before the records
-  constexpr int kCS = chain_ws_slots(NX, NU);   // record: stage Hessian (NH), Sigma (NZ), A (NX^2), B (NX NU)
-  constexpr int kRH = 0, kRS = NH, kRA = NH + NZ, kRB = NH + NZ + NX * NX, kRP = kRB + NX * NU;
-  constexpr int kRZ = kRP + (NX + 1) * NX;  // the iterate across the row chain (stash below)
-  static_assert(!kWsStash || (kRZ + 5 * NZ + NX == kCS && kCS % 2 == 0), "chain stash record");
-  // this thread's record (16-byte aligned: hipMalloc base, 64-thread-multiple stride, even kCS);
-  // opaque, so no address is hoisted out of the solve loop
-  auto wsrec = [&]() __attribute__((always_inline)) -> const double* {
-    double* r = a.ws + (long)kWsH * a.ws_stride + gid * kCS;
-    asm volatile("" : "+v"(r));
-    return (const double*)__builtin_assume_aligned(r, 16);
-  };
+  constexpr ChainRec kRec(NX, NU);
+  auto wsrec = [&]() __attribute__((always_inline)) { return chain_record<Model>(a.ws, a.ws_stride, gid); };
   XWave<G> xw{xch, 0};
   const int inst = (int)(gid / (G * R));
   const int rho = R > 1 ? (int)((threadIdx.x / G) % R) : 0;  // replica of this lane (0: the writer)
@@ -1066,21 +1063,17 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
     if constexpr (kWsStash) {
       double* r = const_cast<double*>(wsrec());
 #pragma unroll
-      for (int i = 0; i < NH; ++i) r[kRH + i] = Hs[i];
+      for (int i = 0; i < NH; ++i) r[kRec.H + i] = Hs[i];
 #pragma unroll
-      for (int i = 0; i < NZ; ++i) r[kRS + i] = sig[i];
+      for (int i = 0; i < NZ; ++i) r[kRec.S + i] = sig[i];
 #pragma unroll
-      for (int i = 0; i < NX * NX; ++i) r[kRA + i] = (Model::AMASK & (1ull << i)) ? A[i] : 0.0;
+      for (int i = 0; i < NX * NX; ++i) r[kRec.A + i] = (Model::AMASK & (1ull << i)) ? A[i] : 0.0;
 #pragma unroll
-      for (int i = 0; i < NX * NU; ++i) r[kRB + i] = (Model::BMASK & (1ull << i)) ? Bm[i] : 0.0;
+      for (int i = 0; i < NX * NU; ++i) r[kRec.B + i] = (Model::BMASK & (1ull << i)) ? Bm[i] : 0.0;
     }
     // this lane's Jacobians back from the workspace (kWsStash), for the phases after the chain
     auto ws_jac = [&](double* Aw, double* Bw) __attribute__((always_inline)) {
-      const double* r = wsrec();
-#pragma unroll
-      for (int i = 0; i < NX * NX; ++i) Aw[i] = (Model::AMASK & (1ull << i)) ? wsload(r, kRA + i) : 0.0;
-#pragma unroll
-      for (int i = 0; i < NX * NU; ++i) Bw[i] = (Model::BMASK & (1ull << i)) ? wsload(r, kRB + i) : 0.0;
+      chain_record_jac<Model>(wsrec(), Aw, Bw);
     };
     double delta = 0.0;
     bool need = !done;  // instance still needs a factorisation
@@ -1101,9 +1094,9 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
       if constexpr (kWsStash) {
         const double* r = wsrec();
 #pragma unroll
-        for (int i = 0; i < NH; ++i) Hd[i] = wsload(r, kRH + i);
+        for (int i = 0; i < NH; ++i) Hd[i] = wsload(r, kRec.H + i);
 #pragma unroll
-        for (int i = 0; i < NZ; ++i) sgv[i] = wsload(r, kRS + i);
+        for (int i = 0; i < NZ; ++i) sgv[i] = wsload(r, kRec.S + i);
       } else {
         const double* Hsrc = Model::hessW(ctx, Hs);
 #pragma unroll
@@ -1119,66 +1112,8 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
       bool okl = true;
       bool seq = true;  // group-uniform: this instance needs the sequential recursion
       if constexpr (Model::kParallelRiccati) {
-        // ---- log-depth associative scan of conditional value functions (pscan.h)
-        RElem<NX> e;
-        bool eok = true;
-        if (hasU) {
-          eok = relem_stage<NX, NU, Model::AMASK, Model::BMASK>(Hd, gp, Aop, Bop, cdef, e);
-        } else {
-          relem_identity<NX>(e);
-          if (hasX) {  // node N: terminal (0, 0, 0, Sigma_x + delta, barrier gradient)
-#pragma unroll
-            for (int i = 0; i < NX * NX; ++i) e.A[i] = 0.0;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-#pragma unroll
-              for (int j = i; j < NX; ++j) e.J[symix(i, j, NX)] = (i == j) ? sgv[i] + delta : 0.0;
-              e.p[i] = gp[i];
-            }
-          }
-        }
-        // Hillis-Steele suffix scan over the whole group through the LDS buffer `sbuf`
-        // (partner = thread t + d; block-uniform trip count, two barriers per level)
-        const int t = (int)threadIdx.x;
-        for (int d = 1; d < G && d <= N; d <<= 1) {
-          relem_store<NX>(e, sbuf, kSBS, t);
-          __syncthreads();
-          if (k + d < G) relem_combine_lds<NX>(e, sbuf + t + d, kSBS);
-          __syncthreads();
-        }
-        // value function of node k+1, then ONE node-parallel Riccati step per lane: gains,
-        // inertia test and (P_k, p_k) as the sequential recursion would produce them
-        double Jn[NP + NX], nx_[NP + NX];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) Jn[i] = e.J[i];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) Jn[NP + i] = e.p[i];
-        group_next<G, NP + NX>(Jn, nx_, xw);
-        const double dl = (k == N) ? 1.0 : 0.0;
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-#pragma unroll
-          for (int j = i; j < NX; ++j) P[symix(i, j, NX)] = (i == j) ? dl * (sgv[i] + delta) : 0.0;
-          p[i] = dl * gp[i];
-        }
-        double dev = 0.0, mag = 1.0;
-        if (hasU) {
-          okl = riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, false, AOneOf<Model>::value>(Hd, gp, Aop, Bop, cdef, nx_,
-                                                                                                 nx_ + NP, P, p, fac);
-#pragma unroll
-          for (int i = 0; i < NP; ++i) {
-            dev = fmax(dev, fabs(P[i] - e.J[i]));
-            mag = fmax(mag, fabs(P[i]));
-          }
-#pragma unroll
-          for (int i = 0; i < NX; ++i) {
-            dev = fmax(dev, fabs(p[i] - e.p[i]));
-            mag = fmax(mag, fabs(p[i]));
-          }
-        }
-        // scan usable: stage R positive definite, finite, and consistent with the step
-        const bool good = eok && dev <= 1e-8 * mag;  // false for NaN
-        seq = !gall<G, G * R>(good, xw);
+        // log-depth scan (pscan.h) and one node-parallel step; seq: the scan's results are not usable
+        seq = backward_scan<Model, G, R>(k, N, hasU, hasX, Hd, sgv, delta, gp, Aop, Bop, cdef, sbuf, xw, P, p, fac, okl);
         DIAG_IF(seq && !done, 8);
       }
       // Stash: the iterate, its bound multipliers, bounds and lam are live across the sequential
@@ -1188,7 +1123,7 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
       constexpr bool kStash = !Model::kParallelRiccati && NX >= 6 && Model::kTrigSlots >= 5 * NZ + NX;
       auto stash = [&](bool back) __attribute__((always_inline)) {
         if constexpr (kStash) {
-          double* t = kRow6 ? const_cast<double*>(wsrec()) + kRZ : tcache + threadIdx.x;
+          double* t = kRow6 ? const_cast<double*>(wsrec()) + kRec.Z : tcache + threadIdx.x;
           constexpr int st = kRow6 ? 1 : kSBS;
           auto mv = [&](double& v, int o) __attribute__((always_inline)) {
             if (back) v = kRow6 ? wsload(t, o) : t[o * st];
@@ -1208,392 +1143,40 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
       };
       stash(false);
       if (__any(seq)) {  // sequential recursion (models without the scan, or its fallback)
+        // P_N = Sigma_x + delta, p_N = barrier gradient (node N's value function)
+        auto terminal = [&](double* Pt, double* pt) __attribute__((always_inline)) {
+          terminal_value<NX>(k, N, sgv, delta, gp, Pt, pt);
+        };
         if (seq && !kRow && !kRow6) {  // (the row chains set P, p after the chain: not live across it)
           okl = true;
-          const double dl = (k == N) ? 1.0 : 0.0;  // P_N = Sigma_x + delta, p_N = barrier gradient
-#pragma unroll
-          for (int i = 0; i < NX; ++i) {
-#pragma unroll
-            for (int j = i; j < NX; ++j) P[symix(i, j, NX)] = (i == j) ? dl * (sgv[i] + delta) : 0.0;
-            p[i] = dl * gp[i];
-          }
+          terminal(P, p);
         }
-        // decoupled suffix: with P_{k+1} reused, s = P_{k+1} c + p_{k+1} needs only p on the
-        // chain; P_{k+1} c comes from the stored Pk of node k+1, off the chain
-        const bool reuse = kDec && pcv && delta == 0.0;  // group-uniform
-        double vpc[kDec ? NX : 1];
-        bool okd = true;
+        // decoupled suffix: a delta = 0 factorisation reuses the stored P_k of the suffix stages
+        DecSuffix<Model> ds;
+        ds.reuse = kDec && pcv && delta == 0.0;  // group-uniform
+        ds.kb = kb;
+        ds.jc = N;
         if constexpr (kDec) {
-          double Pn1[NP];
-          group_next<G, NP>(Pk, Pn1, xw);
-#pragma unroll
-          for (int i = 0; i < NX; ++i) vpc[i] = riccati_pc_row<NX>(Pn1, cdef, i);
-          // reused stages: factors and P_k set here, off the chain (dec_prefactor)
-          if (reuse && k >= kb && k < N) {
-            okd = dec_prefactor<NX, NU>(Hd, fac);
-#pragma unroll
-            for (int i = 0; i < NP; ++i) P[i] = Pk[i];
-          }
+          dec_suffix_setup<Model, G>(k, N, Hd, cdef, Pk, xw, ds, P, fac);
+          ds.jc = dec_suffix_split<G>(ds.reuse, kb, N);
         }
-        // steps j >= jc are reused-suffix steps for every group of the wave: they run first, in
-        // a loop of their own that moves only p (the same operations as the mixed loop's cheap
-        // steps; A stays in the stage table: 25 more live registers here measured slower)
-        int jc = N;
-        if constexpr (kDec) {
-          if (__all(reuse)) {
-            XWave<64> xw1{nullptr, 0};
-            jc = G >= 64 ? kb : (int)greduce<64, OpMax>((double)kb, xw1);  // max over the wave's groups
-            jc = __builtin_amdgcn_readfirstlane(jc);  // wave-uniform: scalar loop bounds
-          }
-        }
-        // The reused suffix as a log-depth scan (multi-wave groups: one instance per block).  On
-        // a reused stage p_k = A^T p_{k+1} + r_k with r_k = gp_x + A^T (P_{k+1} c), and when every
-        // stage of the suffix uses the same table (shared tables) the composition of d steps is
-        // the uniform (A^T)^d: a radix-4 Hillis-Steele suffix scan
-        //   v_k += (A^T)^d v_{k+d} + (A^T)^{2d} v_{k+2d} + (A^T)^{3d} v_{k+3d},   d = 1, 4, 16, 64
-        // carries only the NX-vector through ping-pong LDS buffers, ONE barrier per level (config 5:
-        // 4 levels replace the suffix's 95 dependent steps; a radix-2 scan needs 7 levels of two
-        // barriers).  The powers (A^T)^(j 4^l) depend only on the table: they are formed by NX^2
-        // threads in LDS the first time a launch scans a table and kept there for the launch.
         STAMP_SUB(11);
-        bool sscan = false;  // group-uniform
-        if constexpr (kDec && G > 64) {
-          if (jc < N && !a.lin.per_instance && a.tabseq == nullptr) {
-            const bool mine = k >= jc && k < N;
-            const double ti = (double)((ctx.A - a.lin.A) / (NX * NX));  // my stage's table
-            double tt[2] = {mine ? ti : -1.0, mine ? ti : 1e300};
-            greduce_n<G, 1, 2>(tt, xw);
-            const double tmax = tt[0];
-            sscan = tt[1] == tmax;
-            if (sscan) {
-              double* mpow = dscan + 2 * NX * kSBS;  // (A^T)^(j 4^l) at mpow[(3 l + j - 1) NX^2], row-major
-              const int t = (int)threadIdx.x;
-              constexpr int kLev = G > 64 ? (G <= 256 ? 4 : 5) : 1;  // 4^kLev >= G
-              if (tmax != pow_tab) {  // block-uniform
-                const double* Au = a.lin.A + (size_t)tmax * NX * NX;
-                auto mul = [&](int dst, int x, int y) __attribute__((always_inline)) {  // mpow[dst] = X Y
-                  if (t < NX * NX) {
-                    const double* X = mpow + x * NX * NX;
-                    const double* Y = mpow + y * NX * NX;
-                    const int i = t / NX, j = t % NX;
-                    double acc = X[i * NX] * Y[j];
-#pragma unroll
-                    for (int m = 1; m < NX; ++m) acc = fma(X[i * NX + m], Y[m * NX + j], acc);
-                    mpow[dst * NX * NX + t] = acc;
-                  }
-                  __syncthreads();
-                };
-                if (t < NX * NX) mpow[t] = Au[(t % NX) * NX + t / NX];
-                __syncthreads();
-                for (int l = 0; l < kLev; ++l) {
-                  if (l > 0) mul(3 * l, 3 * l - 2, 3 * l - 2);  // (A^T)^(4^l) = ((A^T)^(2 4^(l-1)))^2
-                  mul(3 * l + 1, 3 * l, 3 * l);                 // (A^T)^(2 4^l)
-                  mul(3 * l + 2, 3 * l + 1, 3 * l);             // (A^T)^(3 4^l)
-                }
-                pow_tab = tmax;
-              }
-              double v[NX];
-#pragma unroll
-              for (int i = 0; i < NX; ++i) {
-                double acc = gp[i];
-#pragma unroll
-                for (int m = 0; m < NX; ++m)
-                  if (Model::AMASK & (1ull << (m * NX + i))) acc = fma(Aop[m * NX + i], vpc[m], acc);
-                v[i] = mine ? acc : (k == N ? p[i] : 0.0);
-              }
-              double* buf = dscan;  // ping-pong: level l reads buf[l % 2], writes buf[(l + 1) % 2]
-#pragma unroll
-              for (int i = 0; i < NX; ++i) buf[i * kSBS + t] = v[i];
-              __syncthreads();
-              for (int l = 0, d = 1; l < kLev && d <= N; ++l, d *= 4) {
-                const double* cur = dscan + (l & 1) * NX * kSBS;
-                double* nxt = dscan + ((l + 1) & 1) * NX * kSBS;
-#pragma unroll
-                for (int q = 1; q <= 3; ++q) {
-                  // the matrix spread over each 16-lane row (lane r: elements r and 16 + r) and
-                  // applied by row-broadcast FMAs (collectives.h matvec_bcast): the block-uniform
-                  // elements were 25 broadcast LDS reads, each a round trip on the FMA chain.  Every
-                  // lane takes part (a broadcast source lane must be active); lanes without a
-                  // partner keep v.
-                  const double* M = mpow + (3 * l + q - 1) * NX * NX;
-                  const int r = t & 15;
-                  const double mA = M[min(r, NX * NX - 1)];  // (in bounds for NX * NX < 16 too)
-                  const double mB = NX * NX > 16 ? M[16 + min(r, NX * NX - 17)] : 0.0;
-                  const bool on = t + q * d < G;
-                  const int src = on ? t + q * d : t;
-                  double w[NX], acc[NX];
-#pragma unroll
-                  for (int i = 0; i < NX; ++i) {
-                    w[i] = cur[i * kSBS + src];
-                    acc[i] = v[i];
-                  }
-                  matvec_bcast<NX>(acc, w, mA, mB);
-#pragma unroll
-                  for (int i = 0; i < NX; ++i) v[i] = on ? acc[i] : v[i];
-                }
-#pragma unroll
-                for (int i = 0; i < NX; ++i) nxt[i * kSBS + t] = v[i];
-                __syncthreads();
-              }
-              if (seq && mine) {
-#pragma unroll
-                for (int i = 0; i < NX; ++i) p[i] = v[i];
-                fac.g0 = gp[NX];
-                if constexpr (NU == 2) fac.g1 = fma(-fac.t, gp[NX], gp[NX + 1]);
-                okl = okd;
-              }
-            }
-          }
-        }
+        bool sscan = false;  // group-uniform: the reused suffix ran as the log-depth scan
+        if constexpr (kDec && G > 64)
+          sscan = suffix_scan<Model, G>(k, N, seq, ds, !a.lin.per_instance && a.tabseq == nullptr, a.lin.A, ctx.A, gp, Aop,
+                                        dscan, pow_tab, xw, p, fac, okl);
         STAMP_SUB(12);
-        if constexpr (kRow) {
-          // the row chain (rowchain.h): the node lanes hand their stages to LDS records, every row runs
-          // its instance's whole recursion, and node lane k takes step k's results back -- the same
-          // operations as riccati_step below, so the same bits
-          static_assert(!kDec && !kWsStash, "row chain: plain sequential recursion only");
-          int rslot = (int)((threadIdx.x & 63) / (G * R)) * G * rowchain::kRec;
-          asm volatile("" : "+v"(rslot));  // (not hoisted out of the solve loop: one register less there)
-          double* rinst = rcbuf + rslot;
-          // P_N = Sigma_x + delta, p_N = barrier gradient (node N's value function)
-          auto terminal = [&](double* Pt, double* pt) __attribute__((always_inline)) {
-            const double dl = (k == N) ? 1.0 : 0.0;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-#pragma unroll
-              for (int j = i; j < NX; ++j) Pt[symix(i, j, NX)] = (i == j) ? dl * (sgv[i] + delta) : 0.0;
-              pt[i] = dl * gp[i];
-            }
-          };
-          if (seq && (R == 1 || rho == 0)) {
-            if (hasU) {
-              rowchain::store_stage(rinst + k * rowchain::kRec, Hd, gp, Aop, Bop, cdef);
-            } else if (hasX && k == N) {
-              double PN[NP], pN[NX];
-              terminal(PN, pN);
-              rowchain::store_terminal(rinst + k * rowchain::kRec, PN, pN);
-            }
-          }
-          // one wave per workgroup (G R <= 64): its LDS accesses complete in issue order, so the
-          // hand-overs need only a compiler barrier, no s_barrier and no wait for the stores
-          static_assert(G * R <= 64, "row chain: single-wave workgroups");
-          asm volatile("" ::: "memory");
-          STAMP_SUB(11);  // (diagnostic build: the chain itself as sub-phase 11, unused by this model)
-          rowchain::run<G * R>(rinst, N);
-          asm volatile("" ::: "memory");
-          STAMP_SUB(12);
-          // every node redoes its own step from node k+1's value function -- the chain's step k, the
-          // same function on the same operands -- for its factors and P_k, all nodes at once.  P, p and
-          // the factors are (re)set only here, so none of them is live across the chain (node N and
-          // the lanes past it: P_N / zeros and no factors, as the sequential recursion leaves them),
-          // and the stage Hessian is formed again from its parts (the delta barrier keeps the compiler
-          // from holding the pre-chain copy across the chain instead)
-          if (seq) {
-            if (hasU) {
-              double Pin_[NP], pin_[NX], Hk[NH];
-              rowchain::load_next(rinst + (k + 1) * rowchain::kRec, Pin_, pin_);
-              double dlt = delta;
-              asm volatile("" : "+v"(dlt));
-              const double* Hsrc = Model::hessW(ctx, Hs);
-#pragma unroll
-              for (int i = 0; i < NH; ++i) Hk[i] = Hsrc[i];
-#pragma unroll
-              for (int i = 0; i < NZ; ++i) Hk[symix(i, i, NZ)] += sgv[i] + dlt;
-              (void)riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, false, AOneOf<Model>::value>(
-                  Hk, gp, Aop, Bop, cdef, Pin_, pin_, P, p, fac);
-            } else {
-              terminal(P, p);
-              fac = Fac<NX, NU>{};
-            }
-            okl = !hasU || fac_ok<NX, NU>(fac);
-          }
-        } else if constexpr (kRow6) {
-          // the 6-state row chain (rowchain6.h): the node lanes write their stages (from the
-          // workspace stash) into the LDS ring window by window, every row runs the instance's
-          // recursion and stores each node's value function into that node's workspace slots, and
-          // node lane k redoes its own step from node k+1's -- the chain's step k, the same
-          // operations as riccati_step, so the same bits -- for its factors and P_k
-          static_assert(!kDec && kWsStash, "6-state row chain: plain sequential recursion, workspace stash");
-          auto fill = [&](int lo, int hi, bool top) __attribute__((always_inline)) {
-            if (seq && hasU && k >= lo && k <= hi) {
-              const double* r = wsrec();
-              double Hs_[NH], sg_[NZ], A_[NX * NX], B_[NX * NU];
-#pragma unroll
-              for (int i = 0; i < NH; ++i) Hs_[i] = wsload(r, kRH + i);
-#pragma unroll
-              for (int i = 0; i < NZ; ++i) sg_[i] = wsload(r, kRS + i);
-              ws_jac(A_, B_);
-              rowchain6::store_node(tcache + (k - lo) * rowchain6::kRec, Hs_, sg_, delta, A_, B_, gp, cdef);
-            }
-            if (top && seq && hasX && k == N)
-              rowchain6::store_terminal(tcache + (N - lo) * rowchain6::kRec, sgv, delta, gp);
-          };
-          double* out0 = a.ws + (long)kWsH * a.ws_stride + (gid - k) * kCS + kRP;  // node 0's slots
-          STAMP_SUB(11);
-          const bool early = rowchain6::run(tcache, out0, kCS, valid && seq, N, fill);
-          __syncthreads();  // row 0's workspace stores, before the node lanes read them
-          STAMP_SUB(12);
-          if (early) {
-            // a step's reduced Huu' failed the inertia test (the chain stopped there): the attempt
-            // fails whatever the other steps give -- the same decision as fac_ok after the full chain
-            okl = false;
-          } else if (seq) {
-            if (hasU) {
-              double Pin_[NP], pin_[NX], Hj[NH], Aj[NX * NX], Bj[NX * NU];
-              rowchain6::load_next(wsrec() + kCS + kRP, Pin_, pin_);
-              ws_jac(Aj, Bj);
-              const double* r = wsrec();
-#pragma unroll
-              for (int i = 0; i < NZ; ++i)
-#pragma unroll
-                for (int jj = i; jj < NZ; ++jj) {
-                  const int t = symix(i, jj, NZ);
-                  Hj[t] = wsload(r, kRH + t);
-                  if (jj == i) Hj[t] += wsload(r, kRS + i) + delta;
-                }
-              (void)riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, false, AOneOf<Model>::value>(
-                  Hj, gp, Aj, Bj, cdef, Pin_, pin_, P, p, fac);
-            } else {
-              const double dl = (k == N) ? 1.0 : 0.0;  // node N: P_N = Sigma_x + delta, p_N = gradient
-#pragma unroll
-              for (int i = 0; i < NX; ++i) {
-#pragma unroll
-                for (int j = i; j < NX; ++j) P[symix(i, j, NX)] = (i == j) ? dl * (sgv[i] + delta) : 0.0;
-                p[i] = dl * gp[i];
-              }
-              fac = Fac<NX, NU>{};
-            }
-            okl = !hasU || fac_ok<NX, NU>(fac);
-          }
-        } else if constexpr (G <= 64) {
-          if constexpr (kDec) {
-            for (int j = N - 1; j >= jc; --j) {
-              double pin_[NX];
-#pragma unroll
-              for (int i = 0; i < NX; ++i) pin_[i] = from_next(p[i]);
-              if (seq && k == j) {
-                dec_vector_step<NX, NU, Model::AMASK, Model::BMASK>(gp, Aop, Bop, vpc, pin_, p, fac);
-                okl = okd;
-              }
-            }
-          }
-          // models with a long chain step (the workspace-stash models, one instance per wave): a
-          // failed inertia test ends the chain early (below)
-          constexpr bool kEarly = kWsStash && !kDec && G == 64;
-          bool early = false;
-          // the chain: one step per node, lane j only.  Models without the decoupled suffix take
-          // the inertia verdict of their step from its factors after the chain, on all lanes at
-          // once (fac_ok), so no lane-mask merge sits on the chain
-#pragma unroll 2
-          for (int j = min(N, jc) - 1; j >= 0; --j) {
-            const bool cheap = reuse && j >= kb;
-            double Pin_[NP], pin_[NX];
-            if (!kDec || __any(!cheap)) {
-#pragma unroll
-              for (int i = 0; i < NP; ++i) Pin_[i] = from_next(P[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < NX; ++i) pin_[i] = from_next(p[i]);
-            if (seq && k == j) {
-              if constexpr (kDec) {
-                if (cheap) {  // group-uniform
-                  dec_vector_step<NX, NU, Model::AMASK, Model::BMASK>(gp, Aop, Bop, vpc, pin_, p, fac);
-                  okl = okd;
-                } else {
-                  okl = riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, kDec, AOneOf<Model>::value>(
-                      Hd, gp, Aop, Bop, cdef, Pin_, pin_, P, p, fac);
-                }
-              } else if constexpr (kWsStash) {
-                // this step's operands from the workspace (lane j only): no lane keeps its stage
-                // Hessian and Jacobians in registers across the chain
-                double Hj[NH], Aj[NX * NX], Bj[NX * NU];
-                ws_jac(Aj, Bj);
-                {
-                  const double* r = wsrec();
-#pragma unroll
-                  for (int i = 0; i < NZ; ++i)
-#pragma unroll
-                    for (int jj = i; jj < NZ; ++jj) {
-                      const int t = symix(i, jj, NZ);
-                      Hj[t] = wsload(r, kRH + t);
-                      if (jj == i) Hj[t] += wsload(r, kRS + i) + delta;
-                    }
-                }
-                (void)riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, kDec, AOneOf<Model>::value>(
-                    Hj, gp, Aj, Bj, cdef, Pin_, pin_, P, p, fac);
-              } else {
-                (void)riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, kDec, AOneOf<Model>::value>(
-                    Hd, gp, Aop, Bop, cdef, Pin_, pin_, P, p, fac);
-              }
-            }
-            // a step whose reduced Huu' is not positive definite decides the attempt: the KKT
-            // matrix has the wrong inertia whatever the remaining steps give, so the chain stops
-            // there (one instance per wave, so the verdict is the wave's).  Same decision, same
-            // delta sequence as running the chain out (fac_ok is the test taken after the chain)
-            if constexpr (kEarly) {
-              if (__any(seq && k == j && !fac_ok<NX, NU>(fac))) {
-                early = true;
-                break;
-              }
-            }
-          }
-          if constexpr (!kDec)
-            if (seq) okl = !early && (!hasU || fac_ok<NX, NU>(fac));
-        } else {  // wave by wave, N-side first; the value function crosses waves through LDS
-          const int wv = (int)(threadIdx.x >> 6);
-          for (int ph = XWave<G>::W - 1; ph >= 0; --ph) {
-            if (wv == ph) {
-              const double* in = xw.prev();  // (P, p) of node 64 (ph + 1), written last phase
-              const int jtop = 64 * ph + 63;
-              if constexpr (kDec) {  // this wave's reused-suffix steps (see jc above)
-                for (int j = min(N - 1, jtop); !sscan && j >= max(jc, 64 * ph); --j) {
-                  double pin_[NX];
-#pragma unroll
-                  for (int i = 0; i < NX; ++i) pin_[i] = from_next(p[i]);
-                  if (j == jtop && lane == 63)
-#pragma unroll
-                    for (int i = 0; i < NX; ++i) pin_[i] = in[NP + i];
-                  if (seq && k == j) {
-                    dec_vector_step<NX, NU, Model::AMASK, Model::BMASK>(gp, Aop, Bop, vpc, pin_, p, fac);
-                    okl = okd;
-                  }
-                }
-              }
-              for (int j = min(min(N - 1, jtop), jc - 1); j >= 64 * ph; --j) {
-                const bool cheap = reuse && j >= kb;
-                double Pin_[NP], pin_[NX];
-                if (!kDec || __any(!cheap)) {
-#pragma unroll
-                  for (int i = 0; i < NP; ++i) Pin_[i] = from_next(P[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < NX; ++i) pin_[i] = from_next(p[i]);
-                if (j == jtop && lane == 63) {
-#pragma unroll
-                  for (int i = 0; i < NP; ++i) Pin_[i] = in[i];
-#pragma unroll
-                  for (int i = 0; i < NX; ++i) pin_[i] = in[NP + i];
-                }
-                if (seq && k == j) {
-                  if (cheap) {  // group-uniform
-                    dec_vector_step<NX, NU, Model::AMASK, Model::BMASK>(gp, Aop, Bop, vpc, pin_, p, fac);
-                    okl = okd;
-                  }
-                  else
-                    okl = riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, kDec, AOneOf<Model>::value>(Hd, gp, Aop, Bop, cdef, Pin_, pin_, P, p,
-                                                                                         fac);
-                }
-              }
-              if (ph > 0 && lane == 0) {
-                double* out = xw.cur();
-#pragma unroll
-                for (int i = 0; i < NP; ++i) out[i] = P[i];
-#pragma unroll
-                for (int i = 0; i < NX; ++i) out[NP + i] = p[i];
-              }
-            }
-            xw.sync();
-          }
-        }
+        if constexpr (kRow)
+          backward_rowchain<Model, G, R>(k, N, hasU, hasX, seq, rho, Hd, Model::hessW(ctx, Hs), sgv, delta, gp, Aop, Bop,
+                                         cdef, terminal, rcbuf, P, p, fac, okl MPCX_STAMP_ARGS);
+        else if constexpr (kRow6)
+          (void)backward_rowchain6<Model>(k, N, hasU, hasX, valid, seq, a.ws, a.ws_stride, gid, sgv, delta, gp, cdef, tcache,
+                                          P, p, fac, okl MPCX_STAMP_ARGS);
+        else if constexpr (G <= 64)
+          backward_chain<Model, G>(k, N, hasU, seq, ds, Hd, delta, gp, Aop, Bop, cdef, a.ws, a.ws_stride, gid, P, p, fac,
+                                   okl);
+        else
+          backward_chain_waves<Model, G>(k, N, seq, ds, sscan, Hd, gp, Aop, Bop, cdef, xw, P, p, fac, okl);
       }
       STAMP_SUB(13);
       stash(true);

@@ -137,13 +137,20 @@ struct RestoWs {
   __host__ __device__ static constexpr int SC(int nx, int nz) { return 6 * nz + 3 * nx; }
   __host__ __device__ static constexpr int slots(int nx, int nu) { return SC(nx, nx + nu) + kScalars; }
 };
-// workspace chain stash of the models with kWsStash (the 6-state bicycle, model 4): the stage
-// Hessian (packed), Sigma, A and B of every lane, after the restoration slots, then the row chain's
-// value function of the lane's node (rowchain6.h: P's columns and p, (nx + 1) nx doubles) and the
-// iterate across the chain (z, zL, zU, bounds, lam)
-__host__ __device__ constexpr int chain_ws_slots(int nx, int nu) {
-  return (nx + nu) * (nx + nu + 1) / 2 + nx + nu + nx * nx + nx * nu + (nx + 1) * nx + 5 * (nx + nu) + nx;
-}
+// workspace chain stash of the models with kWsStash (the 6-state bicycle, model 4), after the
+// restoration slots: one record per lane, fields at these offsets (doubles)
+struct ChainRec {
+  int H;     // stage Hessian (packed upper triangle, nz (nz + 1) / 2)
+  int S;     // Sigma (nz)
+  int A, B;  // Jacobians (nx nx, nx nu)
+  int P;     // the row chain's value function of the lane's node (rowchain6.h: P's columns and p, (nx + 1) nx)
+  int Z;     // the iterate across the chain (z, zL, zU, bounds: 5 nz; lam: nx)
+  int size;
+  __host__ __device__ constexpr ChainRec(int nx, int nu)
+      : H(0), S(H + (nx + nu) * (nx + nu + 1) / 2), A(S + nx + nu), B(A + nx * nx), P(B + nx * nu),
+        Z(P + (nx + 1) * nx), size(Z + 5 * (nx + nu) + nx) {}
+};
+__host__ __device__ constexpr int chain_ws_slots(int nx, int nu) { return ChainRec(nx, nu).size; }
 
 // One solve unit (solve_<model>.hip): what the host needs to know about its stage model and the
 // launches of its kernels, all filled in from the model's type (kernels.h model_ops_of).

@@ -171,3 +171,31 @@ def test_row_chain6_is_the_sequential_recursion(N, delta, indef):
     got = np.stack([b[:, N - 1, q] for q in range(21)], axis=-1)
     want = np.stack([Pk[:, i, j] for i in range(6) for j in range(i, 6)], axis=-1)
     np.testing.assert_allclose(got, want, rtol=1e-8, atol=1e-8 * np.abs(want).max())
+
+
+# ---- backward.h backward_chain_waves: the sequential chain of a 128-lane group (two waves, the value
+# function crossing through the LDS exchange) against the same recursion run as one group
+@pytest.mark.parametrize("N", [64, 65, 127])
+def test_multi_wave_chain_is_the_sequential_recursion(N):
+    """Bit for bit the one-group recursion at every node: N = 64 hands over exactly at the wave
+    boundary (node 64 is the terminal node), 65 one step past it, 127 is the full group."""
+    import torch
+
+    if not os.path.exists(LIB):
+        pytest.fail(f"{LIB} not built (make -C tests/hip)")
+    lib = ctypes.CDLL(LIB)
+    lib.chainwaves_check.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3
+    B, G = 5, 128
+    rng = np.random.default_rng(128000 + 10 * N)
+    scale = np.exp(rng.uniform(-3, 3, (B, G)))
+    x = stages(rng, B, G, scale)
+    d_in = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    o_seq = torch.full((B, G, K_OUT), np.nan, dtype=torch.float64, device="cuda")
+    o_wav = torch.full_like(o_seq, np.nan)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    assert lib.chainwaves_check(N, B, ptr(d_in), ptr(o_seq), ptr(o_wav)) == 0
+    a, b = o_seq.cpu().numpy()[:, :N + 1], o_wav.cpu().numpy()[:, :N + 1]
+    # the recursion ran and what crosses the wave boundary is a number (on these seeds the same
+    # recursion in numpy stays finite at every node, |P| <= 1.1e4)
+    assert np.isfinite(a[:, :, :20]).all()
+    np.testing.assert_array_equal(b.view(np.int64), a.view(np.int64))
