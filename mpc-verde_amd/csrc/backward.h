@@ -6,8 +6,9 @@
 // Jacobians, the defect), picks the strategy and runs the inertia-correction loop around it; every
 // strategy leaves on node lane k the value function (P_k, p_k), the step's factors `fac` and the
 // lane's inertia verdict `okl`, by the operations of riccati_step (riccati.h): the same bits.
-// Operands are arguments (no captures of the kernel's state), so tests/hip/rowchain_check.hip calls
-// the very functions the kernel runs.  Included by kernels.h after its stamp macros and model traits.
+// Operands are arguments (no captures of the kernel's state), so tests/hip/rowchain_check.hip,
+// scan_check.hip and suffix_check.hip call the very functions the kernel runs.  Included by kernels.h
+// after its stamp macros and model traits.
 #pragma once
 
 namespace mpcx {
@@ -109,23 +110,29 @@ __device__ __forceinline__ bool backward_scan(int k, int N, bool hasU, bool hasX
   for (int i = 0; i < NX; ++i) Jn[NP + i] = e.p[i];
   group_next<G, NP + NX>(Jn, nx_, xw);
   terminal_value<NX>(k, N, sgv, delta, gp, P, p);
-  double dev = 0.0, mag = 1.0;
+  // (fmax returns its other operand for a NaN, so dev alone never sees one: the differences' sum
+  // `tot` is finite only if every value is)
+  double dev = 0.0, mag = 1.0, tot = 0.0;
   if (hasU) {
     okl = riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, false, AOneOf<Model>::value>(Hd, gp, Aop, Bop, cdef, nx_,
                                                                                            nx_ + NP, P, p, fac);
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      dev = fmax(dev, fabs(P[i] - e.J[i]));
+      const double di = fabs(P[i] - e.J[i]);
+      dev = fmax(dev, di);
+      tot += di;
       mag = fmax(mag, fabs(P[i]));
     }
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-      dev = fmax(dev, fabs(p[i] - e.p[i]));
+      const double di = fabs(p[i] - e.p[i]);
+      dev = fmax(dev, di);
+      tot += di;
       mag = fmax(mag, fabs(p[i]));
     }
   }
   // scan usable: stage R positive definite, finite, and consistent with the step
-  const bool good = eok && dev <= 1e-8 * mag;  // false for NaN
+  const bool good = eok && dev <= 1e-8 * mag && tot < INFINITY;  // (tot: false for NaN and Inf)
   return !gall<G, G * R>(good, xw);
 }
 
