@@ -343,6 +343,39 @@ int mpcx_rk4_sens(mpcx_handle* h, int32_t B, const double* w, const double* P, d
 int mpcx_rk4_sens_dev(mpcx_handle* h, int32_t B, const double* d_X, const double* d_U, const double* d_xr,
                       double* d_J, void* stream);
 
+/* Sensitivities of the solution to the initial state x0 = P[:nx] (the MPC feedback gain), at a
+ * primal-dual point (w, lam_g, lam_x) as a solve returns it -- no reference counterpart.
+ * With H_k the exact Lagrangian Hessian of stage k, A_k, B_k its Jacobians (stage 0 at (x0, U_0)),
+ *   Sigma_i = zL_i / (w_i - lbw_i) + zU_i / (ubw_i - w_i),  zU = max(lam_x, 0), zL = max(-lam_x, 0)
+ * on the finitely bounded variables (0 elsewhere; X_0 is free), one backward Riccati sweep on
+ * H + Sigma, A, B from P_N = Sigma_x (no regularisation) gives the gains K_k, with
+ * K_0 = -Huu'_0^-1 (Hux_0 + B_0^T P_1 A_0), and
+ *   Phi_0 = I,  Phi_{k+1} = (A_k + B_k K_k) Phi_k,   dX_k/dx0 = Phi_k,   dU_k/dx0 = K_k Phi_k,
+ * followed by one step of iterative refinement on that linear system (residuals in twice the
+ * working precision), so the result holds to a few ulps also where the open loop is unstable.
+ * These are the sensitivities of the BARRIER problem at the multipliers passed in: at a solution
+ * they approach the active-set sensitivities (active variables fixed) as mu -> 0 under strict
+ * complementarity; a weakly active bound gives a value between the two one-sided derivatives.
+ *   dw_dx0  B x n_w x nx, row = index in w (the dX_0/dx0 rows are exactly the identity), or NULL
+ *   K0      B x nu x nx = dU_0/dx0, rows nx..nx+nu of dw_dx0 (the same bits): u ~ u0* + K0 (x - x0);
+ *           or NULL.  At least one of dw_dx0 / K0 must be given.
+ *   flag    B: 0 regular; 1 irregular -- a finitely bounded variable without positive slack, or a
+ *           stage whose reduced Huu' is not positive definite (the derivative of a regularised
+ *           system would be that of another problem, so none is applied).  An irregular instance
+ *           gets NaN in all its outputs; the other instances are unaffected and the call returns 0.
+ *           May be NULL.
+ * Bounds: the precedence of a solve launch -- the host call's own lbw / ubw, then the arrays
+ * installed by mpcx_set_bounds_dev (block 0), then the spec's.  Horizons N >= 64 (lane groups wider
+ * than a wavefront) return MPCX_EINVAL, as do B <= 0, a NULL required pointer and both outputs
+ * NULL; nothing is launched then.  An instance's bits do not depend on the batch it is in.
+ * The device variant only enqueues one launch on `stream`: it never synchronises, allocates nothing
+ * and can be captured in a graph. */
+int mpcx_sens_x0_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                     const double* d_lam_x, double* d_dw_dx0, double* d_K0, int32_t* d_flag, void* stream);
+int mpcx_sens_x0(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                 const double* lam_x, const double* lbw, const double* ubw, double* dw_dx0, double* K0,
+                 int32_t* flag);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,9 @@ struct mpcx_handle {
   int ext_brows = 0, ext_bsteps = 0;
   int ext_xbnd = 0;                          // some row bounds a state of a node >= 1 (the validation pass)
   unsigned long long* d_bcheck = nullptr;    // the validation pass's two result words
+  // outputs of the host-pointer sensitivity call (mpcx_sens_x0), grown on demand
+  size_t cap_sens = 0;
+  double* d_sens = nullptr;
 };
 
 namespace {
@@ -429,6 +432,7 @@ void mpcx_destroy(mpcx_handle* h) {
   dev_free(h->d_sweep);
   dev_free(h->d_ws);
   dev_free(h->d_pcache);
+  dev_free(h->d_sens);
   free_linear(h);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -628,6 +632,29 @@ static mpcx::SolveArgs make_args(const mpcx_handle* h, int B, const SolveIO& io)
   return a;
 }
 
+// a host call's own lbw / ubw (either may be null: the spec's) into the handle's per-call device
+// bounds, on the handle's stream; *xbnd = some state of a node >= 1 is bounded (SolveArgs::xbnd)
+static int stage_call_bounds(mpcx_handle* h, const double* lbw, const double* ubw, int* xbnd) {
+  hipStream_t s = h->stream;
+  std::vector<double> lb, ub;
+  spec_bounds(h->spec, lb, ub);
+  if (lbw) lb.assign(lbw, lbw + h->nw);
+  if (ubw) ub.assign(ubw, ubw + h->nw);
+  for (int i = 0; i < h->spec.nx; ++i) {  // X_0 stays free: it is pinned by g_0
+    lb[i] = -1e20;
+    ub[i] = 1e20;
+  }
+  for (int i = 0; i < h->nw; ++i) {
+    if (!(lb[i] > -1e19)) lb[i] = -1e20;
+    if (!(ub[i] < 1e19)) ub[i] = 1e20;
+  }
+  HIPCHK(hipMemcpyAsync(h->d_lbw_call, lb.data(), h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_ubw_call, ub.data(), h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *xbnd = state_bounded(lb, ub, h->spec.nx, h->spec.nu, h->spec.N);
+  return 0;
+}
+
 // the fused receding-horizon launch of mpcx_step_dev / mpcx_run_dev: the start (cold: X_k = x0, U = 0; duals:
 // from the multipliers too) and the update of P and the warm start in place; `io` holds the outputs
 static mpcx::SolveArgs make_step_args(const mpcx_handle* h, int B, double* d_P, double* d_w0, double* d_lam_g0,
@@ -789,24 +816,8 @@ int mpcx_solve_batch(mpcx_handle* h, int32_t B, const double* P, const double* w
   if (int r = ensure(h, B)) return r;
   hipStream_t s = h->stream;
   int call_xbnd = 0;
-  if (lbw || ubw) {
-    std::vector<double> lb, ub;
-    spec_bounds(h->spec, lb, ub);
-    if (lbw) lb.assign(lbw, lbw + h->nw);
-    if (ubw) ub.assign(ubw, ubw + h->nw);
-    for (int i = 0; i < h->spec.nx; ++i) {  // X_0 stays free: it is pinned by g_0
-      lb[i] = -1e20;
-      ub[i] = 1e20;
-    }
-    for (int i = 0; i < h->nw; ++i) {
-      if (!(lb[i] > -1e19)) lb[i] = -1e20;
-      if (!(ub[i] < 1e19)) ub[i] = 1e20;
-    }
-    HIPCHK(hipMemcpyAsync(h->d_lbw_call, lb.data(), h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->d_ubw_call, ub.data(), h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    call_xbnd = state_bounded(lb, ub, h->spec.nx, h->spec.nu, h->spec.N);
-  }
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
   HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
   if (w0) HIPCHK(hipMemcpyAsync(h->d_w0, w0, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
   if (lam_g0) HIPCHK(hipMemcpyAsync(h->d_lam0, lam_g0, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
@@ -870,6 +881,75 @@ int mpcx_shift_dev(mpcx_handle* h, int32_t B, double* d_P, const double* d_w, do
   const mpcx::ModelOps* ops = mpcx::model_ops(a);
   HIPCHK(ops ? ops->shift(a, d_P, d_w, d_w0_next, d_lam_g, d_lam_g0_next, d_lam_x, d_lam_x0_next, (hipStream_t)stream)
              : hipErrorInvalidValue);
+  return 0;
+}
+
+// what both sensitivity entry points refuse before anything is launched
+static int check_sens_args(const mpcx_handle* h, int B, const void* P, const void* w, const void* lam_g,
+                           const void* lam_x, const void* dw, const void* K0) {
+  if (!h) return fail(MPCX_EINVAL, "null handle");
+  if (B <= 0) return fail(MPCX_EINVAL, "sens_x0: B must be >= 1");
+  if (!P || !w || !lam_g || !lam_x) return fail(MPCX_EINVAL, "sens_x0: P, w, lam_g and lam_x are required");
+  if (!dw && !K0) return fail(MPCX_EINVAL, "sens_x0: at least one of dw_dx0 / K0 must be given");
+  if (h->spec.N >= 64)
+    return fail(MPCX_EINVAL, "sens_x0: horizons N >= 64 (lane groups wider than a wavefront) are not supported");
+  if (int r = check_model_ready(h, B)) return r;
+  return 0;
+}
+
+int mpcx_sens_x0_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                     const double* d_lam_x, double* d_dw_dx0, double* d_K0, int32_t* d_flag, void* stream) {
+  if (int r = check_sens_args(h, B, d_P, d_w, d_lam_g, d_lam_x, d_dw_dx0, d_K0)) return r;
+  if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens(a, d_w, d_lam_g, d_lam_x, d_dw_dx0, d_K0, d_flag, (hipStream_t)stream));
+  return 0;
+}
+
+int mpcx_sens_x0(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                 const double* lam_x, const double* lbw, const double* ubw, double* dw_dx0, double* K0,
+                 int32_t* flag) {
+  if (int r = check_sens_args(h, B, P, w, lam_g, lam_x, dw_dx0, K0)) return r;
+  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  if (int r = ensure(h, B)) return r;
+  hipStream_t s = h->stream;
+  const int nx = h->spec.nx, nu = h->spec.nu;
+  const size_t n_dw = (size_t)B * h->nw * nx, n_k0 = (size_t)B * nu * nx;
+  if (n_dw + n_k0 > h->cap_sens) {
+    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
+    dev_free(h->d_sens);
+    h->cap_sens = 0;
+    HIPCHK(hipMalloc(&h->d_sens, (n_dw + n_k0) * sizeof(double)));
+    h->cap_sens = n_dw + n_k0;
+  }
+  int call_xbnd = 0;
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
+  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  double *d_dw = h->d_sens, *d_k0 = h->d_sens + n_dw;
+  HIPCHK(ops->sens(a, h->d_w, h->d_lam, h->d_lamx, d_dw, d_k0, h->d_status, s));
+  if (dw_dx0) HIPCHK(hipMemcpyAsync(dw_dx0, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (K0) HIPCHK(hipMemcpyAsync(K0, d_k0, n_k0 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return 0;
 }
 

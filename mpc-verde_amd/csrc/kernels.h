@@ -2288,6 +2288,10 @@ __global__ void constraints_kernel(SolveArgs a, const double* __restrict__ W, do
   }
 }
 
+}  // namespace mpcx
+#include "sens.h"  // sensitivities of the solution to x0: a kernel of its own
+namespace mpcx {
+
 // ---- launch helpers (called from capi.cpp) -----------------------------------
 // The solve kernel instantiation a launch picks: G lanes per group, R replicas of it per wave.  A
 // 32-lane group widened to a wave runs replicated (R = 2) where the model has that instantiation;
@@ -2363,6 +2367,20 @@ static hipError_t launch_shift_model(const SolveArgs& a, double* P, const double
   return hipGetLastError();
 }
 
+// sensitivities to x0 (sens.h): always the narrowest lane group, single-wave groups only (the host
+// refuses N >= 64)
+template <class Model>
+static hipError_t launch_sens_model(const SolveArgs& a, const double* W, const double* LG, const double* LX, double* DW,
+                                    double* K0, int32_t* FLAG, hipStream_t stream) {
+  if (a.N >= 64) return hipErrorInvalidValue;
+  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+  const int blocks = (int)(((long)a.B * G + 63) / 64);
+  if (G == 16) hipLaunchKernelGGL((sens_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DW, K0, FLAG);
+  else if (G == 32) hipLaunchKernelGGL((sens_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DW, K0, FLAG);
+  else hipLaunchKernelGGL((sens_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DW, K0, FLAG);
+  return hipGetLastError();
+}
+
 #ifdef MPCX_STAMPS
 // diagnostic build: this unit's setters of its own copies of the stamp/counter pointers
 static int diag_set_stamps(void* d) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_stamps), &d, sizeof(void*)); }
@@ -2389,6 +2407,7 @@ static ModelOps model_ops_of(const char* name) {
                   diag_set_stamps,
                   diag_set_counters,
 #endif
+                  launch_sens_model<Model>,
   };
 }
 

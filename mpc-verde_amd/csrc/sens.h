@@ -1,0 +1,525 @@
+// sens.h -- sensitivities of the MPC solution to the initial state x0 (the feedback gain), one
+// kernel of its own beside the solve kernel.
+//
+// At a primal-dual point (w, lam_g, lam_x) of the barrier problem the derivative of w with respect
+// to x0 = P[:nx] solves the solve kernel's KKT system -- stage Hessians H_k + Sigma_k, Jacobians
+// A_k, B_k -- with a right-hand side that lives in stage 0 only (dX_0 = dx0).  One backward Riccati
+// sweep (delta = 0, zero gradients and defects: they do not enter the matrix part) gives the gains
+// K_k, and the forward sweep is the prefix product of the closed-loop maps,
+//   Phi_0 = I,  Phi_{k+1} = (A_k + B_k K_k) Phi_k,   dX_k/dx0 = Phi_k,   dU_k/dx0 = K_k Phi_k.
+// Unlike the Newton step of the solve, stage 0 keeps its feedback: K_0 = -Huu'_0^-1 (Hux_0 +
+// B_0^T P_1 A_0) is dU_0/dx0 itself (the solve zeroes it, dX_0 being no free direction there).
+//
+// Lane model as in the solve kernel: a lane group of G = 16/32/64 lanes per instance, lane k owns
+// node k.  Always the narrowest group (no widening, no replicas), so an instance's bits do not depend
+// on the batch; single-wave groups only (N <= 63).  The evaluation and the backward sweep are the
+// solve kernel's own functions (Model::derivs through stage_derivs, backward_chain / riccati_step,
+// riccati_gains); the forward sweep is new: a log-depth prefix of NX x NX matrix products over the
+// DPP partners of collectives.h.  One step of iterative refinement follows (sens_refine): the KKT
+// residuals of the result in twice the working precision, and the Riccati solve of them with the
+// same factors as two affine scans -- it takes out the backward sweep's rounding, which an unstable
+// open loop amplifies (the move-blocked cart-pole QP: 1e-13 before, 2e-15 after).
+// Included by kernels.h.
+#pragma once
+
+namespace mpcx {
+
+// out = a b (NX x NX, row-major)
+template <int NX>
+__device__ __forceinline__ void sens_matmul(const double* a, const double* b, double* out) {
+#pragma unroll
+  for (int r = 0; r < NX; ++r)
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      double e = a[r * NX] * b[c];
+#pragma unroll
+      for (int m = 1; m < NX; ++m) e = fma(a[r * NX + m], b[m * NX + c], e);
+      out[r * NX + c] = e;
+    }
+}
+
+// Inclusive prefix product over the lanes of a group: lane k enters with M_k and leaves with
+// M_k M_{k-1} ... M_0.  Kogge-Stone inside each 16-lane row, then the previous rows' totals by row
+// broadcasts (scan_partner / scan_takes: the partners of the solve kernel's affine-map scan, here
+// on matrices only); log2 G levels, every lane busy, no LDS.
+template <int NX, int G>
+__device__ __forceinline__ void sens_prefix_product(int k, double* Am) {
+  auto level = [&](auto dc) __attribute__((always_inline)) {
+    constexpr int d = decltype(dc)::value;
+    if constexpr (d < G) {
+      double Ao[NX * NX];
+#pragma unroll
+      for (int i = 0; i < NX * NX; ++i) Ao[i] = scan_partner<d>(Am[i]);
+      if (scan_takes<d>(k)) {
+        double An[NX * NX];
+        sens_matmul<NX>(Am, Ao, An);
+#pragma unroll
+        for (int i = 0; i < NX * NX; ++i) Am[i] = An[i];
+      }
+    }
+  };
+  level(std::integral_constant<int, 1>{});
+  level(std::integral_constant<int, 2>{});
+  level(std::integral_constant<int, 4>{});
+  level(std::integral_constant<int, 8>{});
+  level(std::integral_constant<int, 16>{});
+  level(std::integral_constant<int, 32>{});
+}
+
+// The same scan on affine maps x -> M x + V (V: NX x NX, one column per right-hand side): lane k
+// enters with (M_k, V_k) and leaves with the composition of the maps of lanes 0..k, so V is the
+// state after them from a zero start.
+template <int NX, int G>
+__device__ __forceinline__ void sens_prefix_affine(int k, double* Am, double* Vm) {
+  auto level = [&](auto dc) __attribute__((always_inline)) {
+    constexpr int d = decltype(dc)::value;
+    if constexpr (d < G) {
+      double Ao[NX * NX], Vo[NX * NX];
+#pragma unroll
+      for (int i = 0; i < NX * NX; ++i) {
+        Ao[i] = scan_partner<d>(Am[i]);
+        Vo[i] = scan_partner<d>(Vm[i]);
+      }
+      if (scan_takes<d>(k)) {
+        double An[NX * NX];
+#pragma unroll
+        for (int r = 0; r < NX; ++r)
+#pragma unroll
+          for (int c = 0; c < NX; ++c) {  // V = M_mine V_partner + V_mine
+            double e = Vm[r * NX + c];
+#pragma unroll
+            for (int m = 0; m < NX; ++m) e = fma(Am[r * NX + m], Vo[m * NX + c], e);
+            An[r * NX + c] = e;
+          }
+#pragma unroll
+        for (int i = 0; i < NX * NX; ++i) Vm[i] = An[i];
+        sens_matmul<NX>(Am, Ao, An);
+#pragma unroll
+        for (int i = 0; i < NX * NX; ++i) Am[i] = An[i];
+      }
+    }
+  };
+  level(std::integral_constant<int, 1>{});
+  level(std::integral_constant<int, 2>{});
+  level(std::integral_constant<int, 4>{});
+  level(std::integral_constant<int, 8>{});
+  level(std::integral_constant<int, 16>{});
+  level(std::integral_constant<int, 32>{});
+}
+
+// Sum of products in twice the working precision (TwoSum / TwoProduct by fma; the compensated dot
+// product): the refinement's residuals cancel to ~1e-13 of their terms, so a plain fma chain would
+// return only its own rounding.
+struct SensAcc {
+  double hi = 0.0, lo = 0.0;
+  __device__ __forceinline__ void add(double v) {
+#pragma clang fp contract(off)  // (a product fused into these sums would void the error terms)
+    const double t = hi + v;
+    const double bb = t - hi;
+    lo += (hi - (t - bb)) + (v - bb);
+    hi = t;
+  }
+  __device__ __forceinline__ void mad(double a, double b) {
+#pragma clang fp contract(off)
+    const double pr = a * b;
+    const double e = fma(a, b, -pr);
+    add(pr);
+    lo += e;
+  }
+  __device__ __forceinline__ double value() const { return hi + lo; }
+};
+
+// One step of iterative refinement of (dX_k, dU_k) = (X, U) on the KKT system the sweeps solved.
+// With the costates lam_k = P_k dX_k, the residuals of the three block rows of node k --
+//   rq_k = Hxx dX_k + Hxu dU_k + A_k^T lam_{k+1} - lam_k   (node N: Sigma_x dX_N - lam_N),
+//   rr_k = Hux dX_k + Huu dU_k + B_k^T lam_{k+1},
+//   d_k  = A_k dX_k + B_k dU_k - dX_{k+1}
+// -- are summed in twice the working precision (SensAcc), node-parallel.  The correction is the
+// Riccati solve of these right-hand sides with the factors already formed, and both of its sweeps
+// are affine scans over the closed-loop maps Acl_k = A_k + B_k K_k:
+//   backward  p_N = rq_N,  p_k = Acl_k^T (p_{k+1} + P_{k+1} d_k) + rq_k + K_k^T rr_k
+//             (run on the lanes in reverse order: node k on the lane of node N - k),
+//   kf_k = -Huu'_k^{-1} (rr_k + B_k^T (p_{k+1} + P_{k+1} d_k)),
+//   forward   dX_0 += 0,  ddX_{k+1} = Acl_k ddX_k + B_k kf_k + d_k,  ddU_k = K_k ddX_k + kf_k.
+// The backward sweep's rounding (relative ~1e-16 times the growth of P_k = Q + A^T P A over an
+// unstable open loop) is what the step removes; X_0 = I stays exact (its correction is an exact 0).
+template <class Model, int G>
+__device__ __forceinline__ void sens_refine(int k, int N, bool hasX, bool hasU, const double* Hd, const double* Aop,
+                                            const double* Bop, const double* P, const Fac<Model::NX, Model::NU>& fac,
+                                            const double* Kk, const double* Acl, double* X, double* U) {
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NP = NX * (NX + 1) / 2, NN = NX * NX;
+  auto H = [&](int i, int j) { return Hd[symix(i, j, NZ)]; };
+  double Ad[NN], Bd[NX * NU];
+#pragma unroll
+  for (int i = 0; i < NN; ++i) Ad[i] = (hasU && (Model::AMASK & (1ull << i))) ? Aop[i] : 0.0;
+#pragma unroll
+  for (int i = 0; i < NX * NU; ++i) Bd[i] = (hasU && (Model::BMASK & (1ull << i))) ? Bop[i] : 0.0;
+  // (lanes beyond node N carry zeros; a neighbour group's values never enter: from_next is read
+  // only where hasU)
+  double Xs[NN], lamk[NN];
+#pragma unroll
+  for (int i = 0; i < NN; ++i) Xs[i] = hasX ? X[i] : 0.0;
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      double e = P[symix(i, 0, NX)] * Xs[c];
+#pragma unroll
+      for (int m = 1; m < NX; ++m) e = fma(P[symix(i, m, NX)], Xs[m * NX + c], e);
+      lamk[i * NX + c] = hasX ? e : 0.0;
+    }
+  double rq[NN], rr[NU * NX], d[NN];
+  {
+    double Xn[NN], Ln[NN];
+#pragma unroll
+    for (int i = 0; i < NN; ++i) {
+      const double xn = from_next(Xs[i]), ln = from_next(lamk[i]);
+      Xn[i] = hasU ? xn : 0.0;
+      Ln[i] = hasU ? ln : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        SensAcc q, e;
+#pragma unroll
+        for (int m = 0; m < NX; ++m) q.mad(H(i, m), Xs[m * NX + c]);
+#pragma unroll
+        for (int l = 0; l < NU; ++l) q.mad(H(i, NX + l), U[l * NX + c]);
+#pragma unroll
+        for (int m = 0; m < NX; ++m)
+          if (Model::AMASK & (1ull << (m * NX + i))) q.mad(Ad[m * NX + i], Ln[m * NX + c]);
+        q.add(-lamk[i * NX + c]);
+        rq[i * NX + c] = hasX ? q.value() : 0.0;
+#pragma unroll
+        for (int m = 0; m < NX; ++m)
+          if (Model::AMASK & (1ull << (i * NX + m))) e.mad(Ad[i * NX + m], Xs[m * NX + c]);
+#pragma unroll
+        for (int l = 0; l < NU; ++l)
+          if (Model::BMASK & (1ull << (i * NU + l))) e.mad(Bd[i * NU + l], U[l * NX + c]);
+        e.add(-Xn[i * NX + c]);
+        d[i * NX + c] = hasU ? e.value() : 0.0;
+      }
+#pragma unroll
+      for (int l = 0; l < NU; ++l) {
+        SensAcc r;
+#pragma unroll
+        for (int m = 0; m < NX; ++m) r.mad(H(NX + l, m), Xs[m * NX + c]);
+#pragma unroll
+        for (int n = 0; n < NU; ++n) r.mad(H(NX + l, NX + n), U[n * NX + c]);
+#pragma unroll
+        for (int m = 0; m < NX; ++m)
+          if (Model::BMASK & (1ull << (m * NU + l))) r.mad(Bd[m * NU + l], Ln[m * NX + c]);
+        rr[l * NX + c] = hasU ? r.value() : 0.0;
+      }
+    }
+  }
+  // t_k = P_{k+1} d_k
+  double t[NN];
+  {
+    double Pn[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const double pn = from_next(P[i]);
+      Pn[i] = hasU ? pn : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        double e = Pn[symix(i, 0, NX)] * d[c];
+#pragma unroll
+        for (int m = 1; m < NX; ++m) e = fma(Pn[symix(i, m, NX)], d[m * NX + c], e);
+        t[i * NX + c] = e;
+      }
+  }
+  // backward sweep on the reversed lanes (k <-> N - k is its own inverse)
+  const int src = ((int)(threadIdx.x & 63) & ~(G - 1)) + (k <= N ? N - k : k);
+  double pk[NN];
+  {
+    double Mb[NN], Vb[NN];
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        double e = rq[i * NX + c];
+#pragma unroll
+        for (int l = 0; l < NU; ++l) e = fma(Kk[l * NX + i], rr[l * NX + c], e);
+#pragma unroll
+        for (int m = 0; m < NX; ++m) e = fma(Acl[m * NX + i], t[m * NX + c], e);
+        Vb[i * NX + c] = hasU ? e : rq[i * NX + c];
+        Mb[i * NX + c] = hasU ? Acl[c * NX + i] : 0.0;
+      }
+#pragma unroll
+    for (int i = 0; i < NN; ++i) {
+      Mb[i] = from_lane(Mb[i], src);
+      Vb[i] = from_lane(Vb[i], src);
+    }
+    sens_prefix_affine<NX, G>(k, Mb, Vb);
+#pragma unroll
+    for (int i = 0; i < NN; ++i) pk[i] = from_lane(Vb[i], src);
+  }
+  // feed-forward kf_k and the forward sweep's offsets c_k = B_k kf_k + d_k
+  double kf[NU * NX], cf[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double s[NX], hu[NU];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const double pn = from_next(pk[i * NX + c]);
+      s[i] = (hasU ? pn : 0.0) + t[i * NX + c];
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      double e = rr[l * NX + c];
+#pragma unroll
+      for (int m = 0; m < NX; ++m) e = fma(Bd[m * NU + l], s[m], e);
+      hu[l] = e;
+    }
+    if constexpr (NU == 1) {
+      kf[c] = hasU ? -fac.r0 * hu[0] : 0.0;
+    } else {
+      const double z1 = fac.r1 * fma(-fac.t, hu[0], hu[1]);
+      kf[NX + c] = hasU ? -z1 : 0.0;
+      kf[c] = hasU ? -fma(fac.r0, hu[0], -fac.t * z1) : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      double e = d[i * NX + c];
+#pragma unroll
+      for (int l = 0; l < NU; ++l) e = fma(Bd[i * NU + l], kf[l * NX + c], e);
+      cf[i * NX + c] = e;
+    }
+  }
+  // forward sweep of the correction: lane k enters with stage k - 1's map (lane 0: identity, 0)
+  double Mf[NN], Vf[NN];
+#pragma unroll
+  for (int i = 0; i < NN; ++i) {
+    const double m = from_prev(Acl[i]), v = from_prev(cf[i]);
+    Mf[i] = (k == 0) ? ((i / NX == i % NX) ? 1.0 : 0.0) : (hasX ? m : 0.0);
+    Vf[i] = (k == 0 || !hasX) ? 0.0 : v;
+  }
+  sens_prefix_affine<NX, G>(k, Mf, Vf);
+#pragma unroll
+  for (int i = 0; i < NN; ++i) X[i] += hasX ? Vf[i] : 0.0;
+#pragma unroll
+  for (int l = 0; l < NU; ++l)
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      double e = kf[l * NX + c];
+#pragma unroll
+      for (int m = 0; m < NX; ++m) e = fma(Kk[l * NX + m], Vf[m * NX + c], e);
+      U[l * NX + c] += hasU ? e : 0.0;
+    }
+}
+
+// W, LG, LX: the point (B x nw, B x ng, B x nw, the solve's outputs); DW: B x nw x NX (row = index
+// in w) or null; K0: B x NU x NX or null; FLAG: B or null (0 regular, 1 irregular: a bounded
+// variable without positive slack, or a stage failing the inertia test -- NaN outputs).
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_kernel(SolveArgs a, const double* __restrict__ W,
+                                                  const double* __restrict__ LG, const double* __restrict__ LX,
+                                                  double* __restrict__ DW, double* __restrict__ K0,
+                                                  int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NH = NZ * (NZ + 1) / 2, NP = NX * (NX + 1) / 2;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N, ng = NX * (N + 1);
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  // LDS value cache of the ODE models' derivative passes (ode.h), as the solve kernel sets it up
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+
+  // ---- parameters, model context, the point
+  const double* Pin = a.P + (size_t)(valid ? inst : 0) * a.p_stride;
+  double x0[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) x0[i] = valid ? Pin[i] : 0.0;
+  const ModelArgs ma = [&] {
+    ModelArgs m = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      m.tc = tcache + threadIdx.x;
+      m.tc_stride = kSBS;
+    }
+    return m;
+  }();
+  typename Model::Ctx ctx;
+  Model::load_ctx(ma, valid ? inst : 0, Pin, k, hasU, ctx);
+
+  double z[NZ] = {}, lam[NX] = {}, lx[NZ] = {};  // lx = zU - zL of my variables (X_0 has none)
+  double lb[NZ], ub[NZ];
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) {
+    lb[i] = -1e20;
+    ub[i] = 1e20;
+  }
+  if (hasX) {
+    const double* w = W + (size_t)inst * nw;
+    const double* l = LX + (size_t)inst * nw;
+    const double* lbr = a.lbw + (size_t)inst * a.bnd_row;
+    const double* ubr = a.ubw + (size_t)inst * a.bnd_row;
+    for (int i = 0; i < NX; ++i) {
+      z[i] = w[ixw<NX, NU>(k, i)];
+      lam[i] = LG[(size_t)inst * ng + NX * k + i];
+      if (XBoundsOf<Model>::value && k > 0) {
+        lx[i] = l[ixw<NX, NU>(k, i)];
+        lb[i] = lbr[ixw<NX, NU>(k, i)];
+        ub[i] = ubr[ixw<NX, NU>(k, i)];
+      }
+    }
+    if (hasU)
+      for (int i = 0; i < NU; ++i) {
+        z[NX + i] = w[iuw<NX, NU>(k, i)];
+        lx[NX + i] = l[iuw<NX, NU>(k, i)];
+        lb[NX + i] = lbr[iuw<NX, NU>(k, i)];
+        ub[NX + i] = ubr[iuw<NX, NU>(k, i)];
+      }
+  }
+
+  // ---- evaluation at fs = 1 with the multipliers as returned (the results section of the solve
+  //      kernel writes lam / fs and (zU - zL) / fs: at fs = 1 its inverse is the identity); lane 0
+  //      evaluates at (x0, U_0), as the solve kernel's stage_point does
+  double ln[NX];
+  group_next<G, NX>(lam, ln, xw);
+  double ze[NZ];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) ze[i] = (k == 0) ? x0[i] : z[i];
+#pragma unroll
+  for (int i = 0; i < NU; ++i) ze[NX + i] = z[NX + i];
+  double xf[NX], qv, A[NX * NX], Bm[NX * NU], gq[NZ], Hs[NH];
+  stage_derivs<Model, G>(ma, ctx, ze, ln, 1.0, xf, qv, A, Bm, gq, Hs);
+
+  // ---- Sigma; a bounded variable without positive slack makes the instance irregular
+  double sig[NZ];
+  bool okl = true;
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) {
+    const bool own = (i < NX) ? hasX : hasU;
+    sig[i] = 0.0;
+    if (own && lb[i] > -kInfBound) {
+      const double s = z[i] - lb[i];
+      okl = okl && s > 0.0;
+      sig[i] += fmax(-lx[i], 0.0) / s;
+    }
+    if (own && ub[i] < kInfBound) {
+      const double s = ub[i] - z[i];
+      okl = okl && s > 0.0;
+      sig[i] += fmax(lx[i], 0.0) / s;
+    }
+  }
+
+  // ---- stage operands: H + Sigma (table-Hessian models: 2 W of the stage table; none at node N)
+  const double* Aop = Model::jacA(ctx, A);
+  const double* Bop = Model::jacB(ctx, Bm);
+  const double* Hsrc = Model::hessW(ctx, Hs);
+  double Hd[NH];
+#pragma unroll
+  for (int i = 0; i < NH; ++i) Hd[i] = hasU ? (Model::kTableHess ? 2.0 * Hsrc[i] : Hsrc[i]) : 0.0;
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) Hd[symix(i, i, NZ)] += sig[i];
+
+  // ---- backward sweep, delta = 0, no inertia correction: P_N = Sigma_x, zero gradients and defects
+  const double zero[NZ] = {};
+  double P[NP], p[NX];
+  terminal_value<NX>(k, N, sig, 0.0, zero, P, p);
+  Fac<NX, NU> fac = {};
+  bool okf = true;
+  if constexpr (WsStashOf<Model>::value) {
+    // (the solve kernel's chain of these models reads its operands from the workspace stash; here
+    // they are in registers, so the chain is written out: the same riccati_step, lane j only)
+    for (int j = N - 1; j >= 0; --j) {
+      double Pin_[NP], pin_[NX];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) Pin_[i] = from_next(P[i]);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) pin_[i] = from_next(p[i]);
+      if (k == j)
+        (void)riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, false, AOneOf<Model>::value>(
+            Hd, zero, Aop, Bop, zero, Pin_, pin_, P, p, fac);
+    }
+    okf = !hasU || fac_ok<NX, NU>(fac);
+  } else {
+    DecSuffix<Model> ds;  // no reused suffix: every step is the full one
+    ds.kb = N + 1;
+    ds.jc = N;
+#pragma unroll
+    for (int i = 0; i < (DecSuffixOf<Model>::value ? NX : 1); ++i) ds.vpc[i] = 0.0;
+    backward_chain<Model, G>(k, N, hasU, true, ds, Hd, 0.0, zero, Aop, Bop, zero, nullptr, 0, gid, P, p, fac, okf);
+  }
+  okl = okl && (!hasU || okf);
+
+  // ---- gains on all lanes; K_0 is kept
+  double Kk[NU * NX], kf[NU];
+  riccati_gains<NX, NU>(fac, Kk, kf);
+  (void)kf;
+#pragma unroll
+  for (int i = 0; i < NU * NX; ++i) Kk[i] = hasU ? Kk[i] : 0.0;
+
+  // ---- forward sweep: lane k enters the prefix product with the closed-loop map of stage k - 1
+  //      (lane 0: the identity, so Phi_0 = I exactly)
+  double Acl[NX * NX], Am[NX * NX];
+#pragma unroll
+  for (int r = 0; r < NX; ++r)
+#pragma unroll
+    for (int m = 0; m < NX; ++m) {
+      double e = (Model::AMASK & (1ull << (r * NX + m))) ? Aop[r * NX + m] : 0.0;
+#pragma unroll
+      for (int l = 0; l < NU; ++l)
+        if (Model::BMASK & (1ull << (r * NU + l))) e = fma(Bop[r * NU + l], Kk[l * NX + m], e);
+      Acl[r * NX + m] = e;
+    }
+#pragma unroll
+  for (int i = 0; i < NX * NX; ++i) {
+    const double prv = from_prev(Acl[i]);
+    Am[i] = (k == 0) ? ((i / NX == i % NX) ? 1.0 : 0.0) : prv;
+  }
+  sens_prefix_product<NX, G>(k, Am);
+  // dU_k/dx0 = K_k Phi_k
+  double Du[NU * NX];
+#pragma unroll
+  for (int l = 0; l < NU; ++l)
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      double e = Kk[l * NX] * Am[c];
+#pragma unroll
+      for (int m = 1; m < NX; ++m) e = fma(Kk[l * NX + m], Am[m * NX + c], e);
+      Du[l * NX + c] = e;
+    }
+
+  // ---- one step of iterative refinement with residuals in twice the working precision
+  sens_refine<Model, G>(k, N, hasX, hasU, Hd, Aop, Bop, P, fac, Kk, Acl, Am, Du);
+
+  // ---- regular: every bounded slack positive, every stage's Huu' positive definite, finite results
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NX * NX; ++i) tot += fabs(Am[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(Du[i]);
+  const bool regular = gall<G>(okl && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  if (DW) {
+    double* dw = DW + (size_t)(valid ? inst : 0) * nw * NX;
+    if (hasX)
+      for (int i = 0; i < NX; ++i)
+        for (int c = 0; c < NX; ++c) dw[(size_t)ixw<NX, NU>(k, i) * NX + c] = regular ? Am[i * NX + c] : nan;
+    if (hasU)
+      for (int l = 0; l < NU; ++l)
+        for (int c = 0; c < NX; ++c) dw[(size_t)iuw<NX, NU>(k, l) * NX + c] = regular ? Du[l * NX + c] : nan;
+  }
+  if (valid && k == 0) {
+    if (K0)
+      for (int i = 0; i < NU * NX; ++i) K0[(size_t)inst * NU * NX + i] = regular ? Du[i] : nan;
+    if (FLAG) FLAG[inst] = regular ? 0 : 1;
+  }
+}
+
+}  // namespace mpcx

@@ -175,6 +175,10 @@ struct ModelOps {
   int (*set_stamps)(void* d_buf);  // diagnostic build: the unit's own copies of the buffer pointers
   int (*set_counters)(void* d_buf);
 #endif
+  // sensitivities of the solution to x0 at the point (W, LG, LX) (sens.h): DW (B x nw x nx) and K0
+  // (B x nu x nx), either may be null; FLAG (B): 1 = irregular instance (NaN outputs)
+  hipError_t (*sens)(const SolveArgs& a, const double* W, const double* LG, const double* LX, double* DW, double* K0,
+                     int32_t* FLAG, hipStream_t stream);
   // doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
   int ws_slots() const { return !resto ? 0 : RestoWs::slots(nx, nu) + (ws_stash ? chain_ws_slots(nx, nu) : 0); }
 };

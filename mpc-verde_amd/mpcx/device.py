@@ -108,6 +108,27 @@ class DeviceLoop:
                                       _ptr(self.lam) if d else None, _ptr(self.lam0) if d else None,
                                       _ptr(self.lamx) if d else None, _ptr(self.lamx0) if d else None, s))
 
+    def sens_x0(self, dw_out=None, K0_out=None, flag_out=None):
+        """Enqueue one sensitivity launch (mpcx_sens_x0_dev) at the loop's resident P, w, lam, lamx:
+        dw_dx0 (B, n_w, nx), K0 (B, nu, nx) -- the feedback gain, u ~ u0* + K0 (x - x0) -- and
+        flag (B,) int32 (1 = irregular instance, NaN outputs), in the kernel's layout (a padded
+        linear model: its pad states included).  Tensors given are written in place, the others are
+        allocated; returns (dw_dx0, K0, flag) without waiting for the stream.  After ``solve()``
+        P still holds the x0 the solution belongs to; ``step()`` has already advanced it."""
+        nw, nx, nu = self.solver._h.n_w, self._knx, self.solver.ocp.nu
+        with torch.cuda.stream(self.stream):
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
+            dw = new((self.B, nw, nx), torch.float64) if dw_out is None else dw_out
+            K0 = new((self.B, nu, nx), torch.float64) if K0_out is None else K0_out
+            flag = new((self.B,), torch.int32) if flag_out is None else flag_out
+        _check(dw, "dw_out", torch.float64, (self.B, nw, nx), self.device)
+        _check(K0, "K0_out", torch.float64, (self.B, nu, nx), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_x0_dev(self.solver._h.ptr, self.B, _ptr(self.P), _ptr(self.w), _ptr(self.lam),
+                                                _ptr(self.lamx), _ptr(dw), _ptr(K0), _ptr(flag),
+                                                ctypes_void(self.stream.cuda_stream)))
+        return dw, K0, flag
+
     def set_stage_refs(self, refs):
         """Per-step stage references (tracking, param layout x0_stageref): refs is a
         (B, N*(nx+nu)) float64 device tensor copied into P[:, nx:] on the loop's stream

@@ -220,6 +220,49 @@ class Solver:
             lam, g = pd.gather(lam, pd.g_idx), pd.gather(g, pd.g_idx)
         return {"w": w, "f": f, "lam_g": lam, "lam_x": lamx, "g": g, "status": st, "iters": it, "t_wall": t}
 
+    def sens_x0(self, P, res, lbw=None, ubw=None):
+        """Sensitivities of the solutions ``res`` (a ``solve_batch`` result: 'w', 'lam_g', 'lam_x') to the
+        initial state x0 = P[:, :nx] (mpcx_sens_x0): one launch of the sensitivity kernel, no solve.
+
+        lbw / ubw: the bounds the solve used -- None (the problem's, or installed device bounds), a
+        scalar or n_w entries shared by the batch.
+        Returns {'dw_dx0': (B, n_w, nx), 'K0': (B, nu, nx), 'flag': (B,)}: row i of dw_dx0[b] is
+        d w_i / d x0 (the X_0 rows are the identity), K0 = dU_0/dx0 is the feedback gain
+        u ~ u0* + K0 (x - x0); flag 1 marks an irregular instance (a variable on its bound, an
+        indefinite reduced Hessian), whose outputs are NaN.  These are the sensitivities of the barrier
+        problem at the multipliers given: the active-set ones to O(mu) at a strictly complementary
+        solution.  The single-shooting form gets the rows of its own w, the controls: (B, N nu, nx)."""
+        P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
+        B = P.shape[0]
+        if P.shape[1] != self.n_p:
+            raise ValueError(f"P: expected {self.n_p} columns, got {P.shape[1]}")
+        nw, ng = self._ms_nw, self._ms_ng
+        w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
+                        for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
+        lbw, ubw = _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw")
+        nx, nu = self.ocp.nx, self.ocp.nu
+        knx = nx
+        pd = self._pad
+        if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
+            P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
+            w, lamx = pd.scatter(w, pd.w_idx, pd.n_w_pad), pd.scatter(lamx, pd.w_idx, pd.n_w_pad)
+            lam = pd.scatter(lam, pd.g_idx, pd.n_g_pad)
+            lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
+            ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
+            nw, knx = pd.n_w_pad, pd.nxp
+        dw = np.empty((B, nw, knx))
+        K0 = np.empty((B, nu, knx))
+        flag = np.empty(B, np.int32)
+        _lib.check(_lib.load().mpcx_sens_x0(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam), _lib.dptr(lamx),
+                                            _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(dw), _lib.dptr(K0),
+                                            _lib.iptr(flag)))
+        if pd is not None:  # the model's own states and inputs only
+            dw, K0 = dw[:, pd.w_idx, :nx], K0[:, :, :nx]
+        if self.ocp.formulation == "single_shooting":
+            nz = nx + nu
+            dw = dw[:, np.concatenate([nx + nz * k + np.arange(nu) for k in range(self.ocp.N)])]
+        return {"dw_dx0": np.ascontiguousarray(dw), "K0": np.ascontiguousarray(K0), "flag": flag}
+
     def rk4_sens(self, w, P):
         """Per-interval defects, costs and Jacobians at w (B, n_w) -- the sweep kernel."""
         if self.ocp.model != "unicycle":

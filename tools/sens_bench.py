@@ -1,0 +1,68 @@
+"""Time of one sensitivity launch (mpcx_sens_x0_dev) next to one lock-step solve of the same batch.
+
+    python tools/sens_bench.py [B] [reps]      (defaults 1024, 9)
+
+Two shapes: config 2 (unicycle point-to-point, N = 20) and the cart-pole QP at N = 50.  Each batch
+is stepped twice (a cold and a warm closed-loop step), then every repetition times one warm
+lock-step step (DeviceLoop.step: solve + fused shift) and one DeviceLoop.sens_x0 launch at the
+loop's resident solution, both with device events, after two warm-up repetitions.  Prints one JSON
+line per shape: medians, min-max spreads, and the ratio sens / solve."""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "mpc-verde_amd"))
+import torch  # noqa: E402
+
+import mpcx  # noqa: E402
+from mpcx import dist, lti  # noqa: E402
+from mpcx.device import DeviceLoop  # noqa: E402
+
+REF_OPTS = {"max_iter": 2000, "acceptable_tol": 1e-8, "acceptable_obj_change_tol": 1e-6}
+
+
+def shapes(B):
+    yield "config2_unicycle_N20", mpcx.unicycle_point_to_point(N=20), dist.config2_inputs(0, B), REF_OPTS
+    lin = lti.inverted_pendulum_qp(N=50)
+    yield "cartpole_qp_N50", lin, lti.pendulum_params(lin, dist.config5_inputs(0, B), 0.0), {"max_iter": 300}
+
+
+def main():
+    B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+    for name, ocp, P, opts in shapes(B):
+        solver = mpcx.nlpsol(name, "mi355x", ocp, {"ipopt": opts})
+        loop = DeviceLoop(solver, P)
+        loop.step()
+        loop.step()
+        dw, K0, flag = loop.sens_x0()
+        its = torch.zeros(B, dtype=torch.int32, device="cuda")
+        solve_ms, sens_ms, it_max = [], [], []
+        for rep in range(reps + 2):
+            a, b, c, d = ev(), ev(), ev(), ev()
+            a.record()
+            loop.step(iters_out=its)
+            b.record()
+            c.record()
+            loop.sens_x0(dw_out=dw, K0_out=K0, flag_out=flag)
+            d.record()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                solve_ms.append(a.elapsed_time(b))
+                sens_ms.append(c.elapsed_time(d))
+                it_max.append(int(its.max()))
+        solve_ms, sens_ms = np.array(solve_ms), np.array(sens_ms)
+        q = lambda v: {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4),  # noqa: E731
+                       "max": round(float(v.max()), 4)}
+        print(json.dumps({"shape": name, "N": ocp.N, "B": B, "reps": reps, "lockstep_step_ms": q(solve_ms),
+                          "sens_x0_ms": q(sens_ms), "ratio_sens_over_step": round(float(np.median(sens_ms) / np.median(solve_ms)), 3),
+                          "ipm_iterations_of_the_steps_max": it_max, "irregular": int(flag.sum()),
+                          "status_gt1": int((loop.status > 1).sum()), "source_hash": mpcx._lib.source_hash()}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
