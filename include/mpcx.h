@@ -376,6 +376,36 @@ int mpcx_sens_x0(mpcx_handle* h, int32_t B, const double* P, const double* w, co
                  const double* lam_x, const double* lbw, const double* ubw, double* dw_dx0, double* K0,
                  int32_t* flag);
 
+/* Directional sensitivities of the solution to the whole parameter row -- x0 and the target x_ref
+ * (MPCX_P_X0_XREF) or the stage references (x_ref_k, u_ref_k) (MPCX_P_X0_STAGEREF) -- at a primal-dual
+ * point as a solve returns it: dw = (dw* / dP) dP for m directions dP, each shaped like a row of P.
+ * One launch, no solve; no reference counterpart.  Along a direction dp the KKT matrix is that of
+ * mpcx_sens_x0 (H_k + Sigma_k, A_k, B_k, stage 0 with its feedback, P_N = Sigma_x) and the right-hand
+ * side is dX_0 = dp[:nx] and, per stage k < N,
+ *   r_k = d(grad_{z_k} l_k)/dp . dp,  l_k = q_k + lam_{k+1}^T f_k   (node cost: -2 W (dx_ref_k, du_ref_k)),
+ *   d_k = d f_k/dp . dp                                            (0 for every supported model).
+ * Backward from p_N = 0: s = p_{k+1} + P_{k+1} d_k, gu = r^u_k + B_k^T s, kf_k = -Huu'_k^-1 gu,
+ * p_k = r^x_k + A_k^T s + K_k^T gu; forward: dU_k = K_k dX_k + kf_k, dX_{k+1} = A_k dX_k + B_k dU_k + d_k;
+ * then one step of iterative refinement on the full system (residuals in twice the working precision).
+ * With the x0 part alone the result is mpcx_sens_x0's to rounding; the first-order predictor of a
+ * parameter change is w(P + dP) ~ w + dw.  Barrier-problem sensitivities, as for mpcx_sens_x0.
+ *   dP    B x m x n_p: m directions per instance, 1 <= m <= nx per call (more: several calls)
+ *   dw    B x n_w x m, row = index in w, column = direction (the dX_0 rows are exactly dP[:, :, :nx];
+ *         rows nx..nx+nu are dU_0).  A column's bits do not depend on the other columns or on m, nor
+ *         an instance's on the batch it is in.
+ *   flag  B: 0 regular, 1 irregular (as mpcx_sens_x0: NaN in all the instance's outputs, the others
+ *         unaffected, the call returns 0).  May be NULL.
+ * Bounds: as mpcx_sens_x0.  MPCX_EINVAL, with nothing launched: a NULL handle, B <= 0, a NULL pointer
+ * other than lbw / ubw / flag, m outside 1..nx, N >= 64, and MPCX_MODEL_PATH_BICYCLE (its stage rows
+ * enter the dynamics).  The device variant only enqueues one launch on `stream`: it never
+ * synchronises, allocates nothing and can be captured in a graph. */
+int mpcx_sens_p_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                    const double* d_lam_x, const double* d_dP, int32_t m, double* d_dw, int32_t* d_flag,
+                    void* stream);
+int mpcx_sens_p(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                const double* lam_x, const double* lbw, const double* ubw, const double* dP, int32_t m, double* dw,
+                int32_t* flag);
+
 #ifdef __cplusplus
 }
 #endif

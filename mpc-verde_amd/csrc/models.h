@@ -91,6 +91,36 @@ struct UnicycleModel {
     const double u2[2] = {z[3], z[4]};
     uni_value(a.sp, z, u2, c.xr, c.ur, xf, q);
   }
+  // Reference tangent of a stage (sens.h sens_p_kernel; no solve kernel calls it): with dc = load_ctx of a
+  // direction dp of the parameter row, r = d(grad_z (q + lam^T F))/dp . dp and d = dF/dp . dp (zero: F reads
+  // no parameter), at fs = 1.  The node cost in closed form.  The quadrature cost's gradient is exactly
+  // affine in (x_ref, u_ref) -- its points s_i(z) do not depend on them -- so r is the difference of derivs'
+  // own gradient at the references dc and 0: no second copy of the moment formulas to keep in step with
+  // the first, and a zero direction gives exact zeros.
+  __device__ __forceinline__ static void ref_tangent(const ModelArgs& a, const Ctx&, const Ctx& dc, const double* z,
+                                                     const double* ln, double* r, double* d) {
+    for (int i = 0; i < 3; ++i) d[i] = 0.0;
+    if (a.sp.cost != 0) {
+      for (int i = 0; i < 3; ++i) r[i] = -2.0 * a.sp.Q[i] * dc.xr[i];
+      for (int i = 0; i < 2; ++i) r[3 + i] = -2.0 * a.sp.R[i] * dc.ur[i];
+      return;
+    }
+    // (one call site run twice, not two inlined copies: the compiler contracts each copy's products and
+    // sums into fmas on its own, and the two gradients of a zero direction would differ by an ulp)
+    double g0[5] = {};
+#pragma unroll 1
+    for (int t = 0; t < 2; ++t) {
+      Ctx rc;
+      for (int i = 0; i < 3; ++i) rc.xr[i] = t == 0 ? 0.0 : dc.xr[i];
+      for (int i = 0; i < 2; ++i) rc.ur[i] = t == 0 ? 0.0 : dc.ur[i];
+      double xf[3], q, A[9], Bm[6], g[5], H[15];
+      derivs(a, rc, z, ln, 1.0, xf, q, A, Bm, g, H);
+      for (int i = 0; i < 5; ++i) {
+        r[i] = g[i] - g0[i];
+        g0[i] = g[i];
+      }
+    }
+  }
 };
 
 // The same model for problems without state bounds (configs 1 and 2: X free, |v| <= 1,
@@ -218,6 +248,19 @@ struct LinearModel {
       acc = fma(dz[i], wi, acc);
     }
     q = acc;
+  }
+  // reference tangent (UnicycleModel::ref_tangent): r = -2 W_j dzr_k, d = 0
+  __device__ __forceinline__ static void ref_tangent(const ModelArgs&, const Ctx& c, const Ctx& dc, const double*,
+                                                     const double*, double* r, double* d) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) d[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      double wi = 0.0;
+#pragma unroll
+      for (int j = 0; j < NZ; ++j) wi = fma(c.W[symix(i, j, NZ)], dc.zr[j], wi);
+      r[i] = -2.0 * wi;
+    }
   }
 };
 

@@ -636,6 +636,17 @@ struct OdeModel {
     }
     if constexpr (kCostHook) Dyn::cost_extra_derivs(a.op.par, c.zr, z, fs, g, H);
   }
+  // reference tangent (UnicycleModel::ref_tangent) of the diagonal node cost: r_i = -2 wgt_i dzr_i, d = 0.
+  // Not for a model whose stage row enters f or a cost hook (kHooks: the path-frame bicycle); the
+  // sensitivity launch refuses it.
+  __device__ __forceinline__ static void ref_tangent(const ModelArgs& a, const Ctx&, const Ctx& dc, const double*,
+                                                     const double*, double* r, double* d) {
+    static_assert(!kHooks, "the stage row enters the dynamics: no reference tangent");
+#pragma unroll
+    for (int i = 0; i < NX; ++i) d[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) r[i] = -2.0 * wgt(a, i) * dc.zr[i];
+  }
   // Exact derivatives by forward sensitivities and stage adjoints (Dyn::kAdjoint: closed-form
   // partials of f).  Everything in RK4 but f is linear, so with mu_e the adjoint of stage e's f
   // value in lam^T F and Tv_e = dv_e/dz the sensitivity of the variables f reads at stage e,

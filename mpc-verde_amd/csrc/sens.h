@@ -19,6 +19,8 @@
 // residuals of the result in twice the working precision, and the Riccati solve of them with the
 // same factors as two affine scans -- it takes out the backward sweep's rounding, which an unstable
 // open loop amplifies (the move-blocked cart-pole QP: 1e-13 before, 2e-15 after).
+// The second kernel of the file, sens_p_kernel (below), solves the same system for
+// directions of the whole parameter row: the references and targets beside x0.
 // Included by kernels.h.
 #pragma once
 
@@ -143,10 +145,17 @@ struct SensAcc {
 //   forward   dX_0 += 0,  ddX_{k+1} = Acl_k ddX_k + B_k kf_k + d_k,  ddU_k = K_k ddX_k + kf_k.
 // The backward sweep's rounding (relative ~1e-16 times the growth of P_k = Q + A^T P A over an
 // unstable open loop) is what the step removes; X_0 = I stays exact (its correction is an exact 0).
-template <class Model, int G>
+//
+// kRhs (sens_p_kernel): the same system with right-hand sides -- rq_k += Rq_k, rr_k += Rr_k, d_k += Dd_k
+// (each NX columns wide, zero where the node has no stage) -- and the costates lam_k = P_k dX_k + pk_k,
+// pk being carried: the sweep's p_k is added to it.  From X = (dx0 on node 0, else 0), U = 0, pk = 0
+// one call is the Riccati solve of the right-hand sides, a second one its refinement.
+template <class Model, int G, bool kRhs = false>
 __device__ __forceinline__ void sens_refine(int k, int N, bool hasX, bool hasU, const double* Hd, const double* Aop,
                                             const double* Bop, const double* P, const Fac<Model::NX, Model::NU>& fac,
-                                            const double* Kk, const double* Acl, double* X, double* U) {
+                                            const double* Kk, const double* Acl, double* X, double* U,
+                                            const double* Rq = nullptr, const double* Rr = nullptr,
+                                            const double* Dd = nullptr, double* pkc = nullptr) {
   constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NP = NX * (NX + 1) / 2, NN = NX * NX;
   auto H = [&](int i, int j) { return Hd[symix(i, j, NZ)]; };
   double Ad[NN], Bd[NX * NU];
@@ -166,6 +175,7 @@ __device__ __forceinline__ void sens_refine(int k, int N, bool hasX, bool hasU, 
       double e = P[symix(i, 0, NX)] * Xs[c];
 #pragma unroll
       for (int m = 1; m < NX; ++m) e = fma(P[symix(i, m, NX)], Xs[m * NX + c], e);
+      if constexpr (kRhs) e += pkc[i * NX + c];
       lamk[i * NX + c] = hasX ? e : 0.0;
     }
   double rq[NN], rr[NU * NX], d[NN];
@@ -190,6 +200,7 @@ __device__ __forceinline__ void sens_refine(int k, int N, bool hasX, bool hasU, 
         for (int m = 0; m < NX; ++m)
           if (Model::AMASK & (1ull << (m * NX + i))) q.mad(Ad[m * NX + i], Ln[m * NX + c]);
         q.add(-lamk[i * NX + c]);
+        if constexpr (kRhs) q.add(Rq[i * NX + c]);
         rq[i * NX + c] = hasX ? q.value() : 0.0;
 #pragma unroll
         for (int m = 0; m < NX; ++m)
@@ -198,6 +209,7 @@ __device__ __forceinline__ void sens_refine(int k, int N, bool hasX, bool hasU, 
         for (int l = 0; l < NU; ++l)
           if (Model::BMASK & (1ull << (i * NU + l))) e.mad(Bd[i * NU + l], U[l * NX + c]);
         e.add(-Xn[i * NX + c]);
+        if constexpr (kRhs) e.add(Dd[i * NX + c]);
         d[i * NX + c] = hasU ? e.value() : 0.0;
       }
 #pragma unroll
@@ -210,6 +222,7 @@ __device__ __forceinline__ void sens_refine(int k, int N, bool hasX, bool hasU, 
 #pragma unroll
         for (int m = 0; m < NX; ++m)
           if (Model::BMASK & (1ull << (m * NU + l))) r.mad(Bd[m * NU + l], Ln[m * NX + c]);
+        if constexpr (kRhs) r.add(Rr[l * NX + c]);
         rr[l * NX + c] = hasU ? r.value() : 0.0;
       }
     }
@@ -259,6 +272,9 @@ __device__ __forceinline__ void sens_refine(int k, int N, bool hasX, bool hasU, 
 #pragma unroll
     for (int i = 0; i < NN; ++i) pk[i] = from_lane(Vb[i], src);
   }
+  if constexpr (kRhs)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) pkc[i] += hasX ? pk[i] : 0.0;
   // feed-forward kf_k and the forward sweep's offsets c_k = B_k kf_k + d_k
   double kf[NU * NX], cf[NN];
 #pragma unroll
@@ -520,6 +536,261 @@ __global__ __launch_bounds__(64) void sens_kernel(SolveArgs a, const double* __r
       for (int i = 0; i < NU * NX; ++i) K0[(size_t)inst * NU * NX + i] = regular ? Du[i] : nan;
     if (FLAG) FLAG[inst] = regular ? 0 : 1;
   }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Directional sensitivities to the whole parameter row P = (x0, references): dw = (dw*/dP) dP for up
+// to NX directions per launch.  A parameter direction is the KKT matrix of sens_kernel
+// with another right-hand side: dX_0 = dp[:nx], and per stage r_k = d(grad_z l_k)/dp . dp,
+// d_k = df_k/dp . dp from the model's reference tangent (Model::ref_tangent on load_ctx of the
+// direction row, which maps a row of either layout onto its stage).  The solve of right-hand sides is
+// the refinement's (sens_refine<.., true>): the factors' two affine scans, once from (dX_0 = dx0,
+// everything else zero) for the solution and once more for its refinement, so no dependent chain
+// beyond the backward factorisation is added.  Every column is an independent right-hand side of the
+// scans (a column's bits do not depend on the others; the unused ones are zeros).
+
+// a model whose stage row enters its dynamics or cost hooks (ode.h kHooks): no reference tangent
+template <class M, class = void>
+struct RefTangentOf {
+  static constexpr bool value = true;
+};
+template <class M>
+struct RefTangentOf<M, std::void_t<decltype(M::kHooks)>> {
+  static constexpr bool value = !M::kHooks;
+};
+
+// The stage operands and Riccati factors of an instance at its point, formed as sens_kernel forms
+// them (the same evaluation, Sigma, backward sweep without inertia correction and gains).
+template <class Model>
+struct SensSys {
+  static constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU;
+  typename Model::Ctx ctx;
+  double ze[NZ], ln[NX];                     // the stage's evaluation point and next costate
+  double A[NX * NX], Bm[NX * NU], Hs[NZ * (NZ + 1) / 2];
+  double Hd[NZ * (NZ + 1) / 2], P[NX * (NX + 1) / 2], Kk[NU * NX], Acl[NX * NX];
+  Fac<NX, NU> fac;
+  bool ok;  // every bounded slack of my variables positive, my stage's Huu' positive definite
+};
+
+template <class Model, int G>
+__device__ __forceinline__ void sens_factor(const SolveArgs& a, const ModelArgs& ma, const double* __restrict__ W,
+                                            const double* __restrict__ LG, const double* __restrict__ LX, long gid,
+                                            int k, int inst, bool valid, SensSys<Model>& s) {
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NH = NZ * (NZ + 1) / 2, NP = NX * (NX + 1) / 2;
+  const int N = a.N;
+  const int nw = NX + NZ * N, ng = NX * (N + 1);
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  const double* Pin = a.P + (size_t)(valid ? inst : 0) * a.p_stride;
+  double x0[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) x0[i] = valid ? Pin[i] : 0.0;
+  Model::load_ctx(ma, valid ? inst : 0, Pin, k, hasU, s.ctx);
+
+  double z[NZ] = {}, lam[NX] = {}, lx[NZ] = {};  // lx = zU - zL of my variables (X_0 has none)
+  double lb[NZ], ub[NZ];
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) {
+    lb[i] = -1e20;
+    ub[i] = 1e20;
+  }
+  if (hasX) {
+    const double* w = W + (size_t)inst * nw;
+    const double* l = LX + (size_t)inst * nw;
+    const double* lbr = a.lbw + (size_t)inst * a.bnd_row;
+    const double* ubr = a.ubw + (size_t)inst * a.bnd_row;
+    for (int i = 0; i < NX; ++i) {
+      z[i] = w[ixw<NX, NU>(k, i)];
+      lam[i] = LG[(size_t)inst * ng + NX * k + i];
+      if (XBoundsOf<Model>::value && k > 0) {
+        lx[i] = l[ixw<NX, NU>(k, i)];
+        lb[i] = lbr[ixw<NX, NU>(k, i)];
+        ub[i] = ubr[ixw<NX, NU>(k, i)];
+      }
+    }
+    if (hasU)
+      for (int i = 0; i < NU; ++i) {
+        z[NX + i] = w[iuw<NX, NU>(k, i)];
+        lx[NX + i] = l[iuw<NX, NU>(k, i)];
+        lb[NX + i] = lbr[iuw<NX, NU>(k, i)];
+        ub[NX + i] = ubr[iuw<NX, NU>(k, i)];
+      }
+  }
+
+  // evaluation at fs = 1 with the multipliers as returned; lane 0 evaluates at (x0, U_0)
+  group_next<G, NX>(lam, s.ln, xw);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) s.ze[i] = (k == 0) ? x0[i] : z[i];
+#pragma unroll
+  for (int i = 0; i < NU; ++i) s.ze[NX + i] = z[NX + i];
+  double xf[NX], qv, gq[NZ];
+  stage_derivs<Model, G>(ma, s.ctx, s.ze, s.ln, 1.0, xf, qv, s.A, s.Bm, gq, s.Hs);
+
+  // Sigma; a bounded variable without positive slack makes the instance irregular
+  double sig[NZ];
+  bool okl = true;
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) {
+    const bool own = (i < NX) ? hasX : hasU;
+    sig[i] = 0.0;
+    if (own && lb[i] > -kInfBound) {
+      const double sl = z[i] - lb[i];
+      okl = okl && sl > 0.0;
+      sig[i] += fmax(-lx[i], 0.0) / sl;
+    }
+    if (own && ub[i] < kInfBound) {
+      const double sl = ub[i] - z[i];
+      okl = okl && sl > 0.0;
+      sig[i] += fmax(lx[i], 0.0) / sl;
+    }
+  }
+
+  // stage operands: H + Sigma (table-Hessian models: 2 W of the stage table; none at node N)
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+  const double* Hsrc = Model::hessW(s.ctx, s.Hs);
+#pragma unroll
+  for (int i = 0; i < NH; ++i) s.Hd[i] = hasU ? (Model::kTableHess ? 2.0 * Hsrc[i] : Hsrc[i]) : 0.0;
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) s.Hd[symix(i, i, NZ)] += sig[i];
+
+  // backward sweep, delta = 0, no inertia correction: P_N = Sigma_x, zero gradients and defects
+  const double zero[NZ] = {};
+  double p[NX];
+  terminal_value<NX>(k, N, sig, 0.0, zero, s.P, p);
+  s.fac = {};
+  bool okf = true;
+  if constexpr (WsStashOf<Model>::value) {
+    for (int j = N - 1; j >= 0; --j) {  // (the chain written out, as in sens_kernel)
+      double Pin_[NP], pin_[NX];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) Pin_[i] = from_next(s.P[i]);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) pin_[i] = from_next(p[i]);
+      if (k == j)
+        (void)riccati_step<NX, NU, Model::AMASK, Model::BMASK, false, false, AOneOf<Model>::value>(
+            s.Hd, zero, Aop, Bop, zero, Pin_, pin_, s.P, p, s.fac);
+    }
+    okf = !hasU || fac_ok<NX, NU>(s.fac);
+  } else {
+    DecSuffix<Model> ds;  // no reused suffix: every step is the full one
+    ds.kb = N + 1;
+    ds.jc = N;
+#pragma unroll
+    for (int i = 0; i < (DecSuffixOf<Model>::value ? NX : 1); ++i) ds.vpc[i] = 0.0;
+    backward_chain<Model, G>(k, N, hasU, true, ds, s.Hd, 0.0, zero, Aop, Bop, zero, nullptr, 0, gid, s.P, p, s.fac, okf);
+  }
+  s.ok = okl && (!hasU || okf);
+
+  // gains on all lanes (K_0 is kept) and the closed-loop maps Acl_k = A_k + B_k K_k
+  double kf[NU];
+  riccati_gains<NX, NU>(s.fac, s.Kk, kf);
+  (void)kf;
+#pragma unroll
+  for (int i = 0; i < NU * NX; ++i) s.Kk[i] = hasU ? s.Kk[i] : 0.0;
+#pragma unroll
+  for (int r = 0; r < NX; ++r)
+#pragma unroll
+    for (int m = 0; m < NX; ++m) {
+      double e = (Model::AMASK & (1ull << (r * NX + m))) ? Aop[r * NX + m] : 0.0;
+#pragma unroll
+      for (int l = 0; l < NU; ++l)
+        if (Model::BMASK & (1ull << (r * NU + l))) e = fma(Bop[r * NU + l], s.Kk[l * NX + m], e);
+      s.Acl[r * NX + m] = e;
+    }
+}
+
+// W, LG, LX: the point, as for sens_kernel; DP: B x m x p_stride directions, each a row of P;
+// DW: B x nw x m (row = index in w, column = direction); FLAG: B or null (sens_kernel's).  1 <= m <= NX.
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_p_kernel(SolveArgs a, const double* __restrict__ W,
+                                                    const double* __restrict__ LG, const double* __restrict__ LX,
+                                                    const double* __restrict__ DP, int m, double* __restrict__ DW,
+                                                    int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+
+  // ---- right-hand sides, one column per direction: the stage's reference tangent, dx0 on node 0
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double r[NZ] = {}, d[NX] = {}, dx0[NX] = {};
+    if (c < m) {  // (launch-uniform)
+      const double* dp = DP + ((size_t)(valid ? inst : 0) * m + c) * a.p_stride;
+      typename Model::Ctx dc;
+      Model::load_ctx(ma, valid ? inst : 0, dp, k, hasU, dc);
+      Model::ref_tangent(ma, s.ctx, dc, s.ze, s.ln, r, d);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) dx0[i] = dp[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      Rq[i * NX + c] = hasU ? r[i] : 0.0;
+      Dd[i * NX + c] = hasU ? d[i] : 0.0;
+      X[i * NX + c] = (valid && k == 0) ? dx0[i] : 0.0;
+      pk[i * NX + c] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      Rr[l * NX + c] = hasU ? r[NX + l] : 0.0;
+      U[l * NX + c] = 0.0;
+    }
+  }
+
+  // ---- the Riccati solve of the right-hand sides, then one step of iterative refinement: the same
+  //      round twice (residuals of the full system in twice the working precision, their solve by the
+  //      two affine scans); dX_0 = dx0 stays exact (its correction is an exact 0)
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  // ---- regular: as sens_kernel
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  double* dw = DW + (size_t)(valid ? inst : 0) * nw * m;
+  if (hasX)
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)ixw<NX, NU>(k, i) * m + c] = regular ? X[i * NX + c] : nan;
+  if (hasU)
+    for (int l = 0; l < NU; ++l)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)iuw<NX, NU>(k, l) * m + c] = regular ? U[l * NX + c] : nan;
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
 }
 
 }  // namespace mpcx

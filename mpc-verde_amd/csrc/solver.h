@@ -179,6 +179,10 @@ struct ModelOps {
   // (B x nu x nx), either may be null; FLAG (B): 1 = irregular instance (NaN outputs)
   hipError_t (*sens)(const SolveArgs& a, const double* W, const double* LG, const double* LX, double* DW, double* K0,
                      int32_t* FLAG, hipStream_t stream);
+  // directional sensitivities to the whole parameter row at the same point (sens.h sens_p_kernel): DP
+  // (B x m x p_stride) directions shaped like rows of P, 1 <= m <= nx; DW (B x nw x m); FLAG as above
+  hipError_t (*sens_p)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* DP, int m,
+                       double* DW, int32_t* FLAG, hipStream_t stream);
   // doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
   int ws_slots() const { return !resto ? 0 : RestoWs::slots(nx, nu) + (ws_stash ? chain_ws_slots(nx, nu) : 0); }
 };

@@ -129,6 +129,28 @@ class DeviceLoop:
                                                 ctypes_void(self.stream.cuda_stream)))
         return dw, K0, flag
 
+    def sens_p(self, dP, dw_out=None, flag_out=None):
+        """Enqueue one parameter-sensitivity launch (mpcx_sens_p_dev) at the loop's resident P, w, lam,
+        lamx: dP (B, m, n_p) float64 device tensor of m <= nx directions, each shaped like a row of the
+        resident P (the kernel's layout: a padded linear model's pad entries included), gives
+        dw (B, n_w, m), the first-order change of w along each direction, and flag (B,) int32
+        (1 = irregular instance, NaN outputs).  Tensors given are written in place, the others are
+        allocated; returns (dw, flag) without waiting for the stream."""
+        nw, nx = self.solver._h.n_w, self._knx
+        if not isinstance(dP, torch.Tensor) or dP.dim() != 3 or not 1 <= dP.shape[1] <= nx:
+            raise ValueError(f"dP: expected a ({self.B}, m, {self.P.shape[1]}) tensor with 1 <= m <= {nx}")
+        m = dP.shape[1]
+        _check(dP, "dP", torch.float64, (self.B, m, self.P.shape[1]), self.device)
+        with torch.cuda.stream(self.stream):
+            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_p_dev(self.solver._h.ptr, self.B, _ptr(self.P), _ptr(self.w), _ptr(self.lam),
+                                               _ptr(self.lamx), _ptr(dP), m, _ptr(dw), _ptr(flag),
+                                               ctypes_void(self.stream.cuda_stream)))
+        return dw, flag
+
     def set_stage_refs(self, refs):
         """Per-step stage references (tracking, param layout x0_stageref): refs is a
         (B, N*(nx+nu)) float64 device tensor copied into P[:, nx:] on the loop's stream

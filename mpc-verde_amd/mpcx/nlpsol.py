@@ -263,6 +263,77 @@ class Solver:
             dw = dw[:, np.concatenate([nx + nz * k + np.arange(nu) for k in range(self.ocp.N)])]
         return {"dw_dx0": np.ascontiguousarray(dw), "K0": np.ascontiguousarray(K0), "flag": flag}
 
+    def sens_p(self, P, res, dP, lbw=None, ubw=None):
+        """Directional sensitivities of the solutions ``res`` to the whole parameter row -- x0 and the
+        target or the stage references -- (mpcx_sens_p): dw = (d w*/d P) dP, no solve.
+
+        dP: (B, m, n_p) directions, each shaped like a row of P, or (B, n_p) for a single one; any m
+        (launches of at most nx columns each; a column's bits do not depend on the others).
+        lbw / ubw: as for :meth:`sens_x0`.
+        Returns {'dw': (B, n_w, m), 'du0': (B, nu, m), 'flag': (B,)}: column j of dw[b] is the
+        first-order change of w along dP[b, j] -- w(P + dP) ~ w + dw -- du0 its rows of U_0, and
+        flag 1 marks an irregular instance (NaN outputs), as :meth:`sens_x0`.  The X_0 rows are
+        dP[:, :, :nx].  The single-shooting form gets the control rows.  Not for the path-frame
+        bicycle (its stage rows enter the dynamics)."""
+        P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
+        B = P.shape[0]
+        if P.shape[1] != self.n_p:
+            raise ValueError(f"P: expected {self.n_p} columns, got {P.shape[1]}")
+        dP = np.asarray(dP, np.float64)
+        if dP.ndim == 2:
+            dP = dP[:, None, :]
+        if dP.ndim != 3 or dP.shape[0] != B or dP.shape[2] != self.n_p or dP.shape[1] < 1:
+            raise ValueError(f"dP: expected ({B}, m, {self.n_p}) or ({B}, {self.n_p}), got {dP.shape}")
+        m = dP.shape[1]
+        nw, ng = self._ms_nw, self._ms_ng
+        w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
+                        for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
+        lbw, ubw = _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw")
+        nx, nu = self.ocp.nx, self.ocp.nu
+        knx = nx
+        pd = self._pad
+        if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
+            P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
+            dP = pd.scatter(dP.reshape(B * m, -1), pd.p_idx, pd.n_p_pad).reshape(B, m, -1)
+            w, lamx = pd.scatter(w, pd.w_idx, pd.n_w_pad), pd.scatter(lamx, pd.w_idx, pd.n_w_pad)
+            lam = pd.scatter(lam, pd.g_idx, pd.n_g_pad)
+            lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
+            ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
+            nw, knx = pd.n_w_pad, pd.nxp
+        dw = np.empty((B, nw, m))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+        for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
+            mc = min(knx, m - c0)
+            part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
+            dPc = np.ascontiguousarray(dP[:, c0:c0 + mc])
+            _lib.check(lib.mpcx_sens_p(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam), _lib.dptr(lamx),
+                                       _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(dPc), mc, _lib.dptr(part),
+                                       _lib.iptr(fl)))
+            dw[:, :, c0:c0 + mc] = part
+            flag |= fl
+        if pd is not None:  # the model's own states and inputs only
+            dw = dw[:, pd.w_idx]
+        du0 = dw[:, nx:nx + nu]
+        if self.ocp.formulation == "single_shooting":
+            nz = nx + nu
+            dw = dw[:, np.concatenate([nx + nz * k + np.arange(nu) for k in range(self.ocp.N)])]
+        return {"dw": np.ascontiguousarray(dw), "du0": np.ascontiguousarray(du0), "flag": flag}
+
+    def sens_xref(self, P, res, lbw=None, ubw=None):
+        """Sensitivities of the solutions ``res`` to the target x_ref of the x0_xref parameter layout
+        (:meth:`sens_p` with the identity directions on x_ref).  Returns {'dw_dxref': (B, n_w, nx),
+        'Kr': (B, nu, nx) = dU_0/dx_ref, 'flag'}: with :meth:`sens_x0`'s gain,
+        u ~ u0* + K0 (x - x0) + Kr (x_ref' - x_ref)."""
+        if self.ocp.param != "x0_xref":
+            raise ValueError("sens_xref: the parameter layout has no target x_ref (stage references: use sens_p)")
+        nx = self.ocp.nx
+        B = np.atleast_2d(np.asarray(P)).shape[0]
+        dP = np.zeros((B, nx, self.n_p))
+        dP[:, np.arange(nx), nx + np.arange(nx)] = 1.0
+        s = self.sens_p(P, res, dP, lbw, ubw)
+        return {"dw_dxref": s["dw"], "Kr": s["du0"], "flag": s["flag"]}
+
     def rk4_sens(self, w, P):
         """Per-interval defects, costs and Jacobians at w (B, n_w) -- the sweep kernel."""
         if self.ocp.model != "unicycle":

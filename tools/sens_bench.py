@@ -1,12 +1,13 @@
-"""Time of one sensitivity launch (mpcx_sens_x0_dev) next to one lock-step solve of the same batch.
+"""Time of one sensitivity launch (mpcx_sens_x0_dev, mpcx_sens_p_dev) next to one lock-step solve of the same batch.
 
     python tools/sens_bench.py [B] [reps]      (defaults 1024, 9)
 
 Two shapes: config 2 (unicycle point-to-point, N = 20) and the cart-pole QP at N = 50.  Each batch
 is stepped twice (a cold and a warm closed-loop step), then every repetition times one warm
-lock-step step (DeviceLoop.step: solve + fused shift) and one DeviceLoop.sens_x0 launch at the
-loop's resident solution, both with device events, after two warm-up repetitions.  Prints one JSON
-line per shape: medians, min-max spreads, and the ratio sens / solve."""
+lock-step step (DeviceLoop.step: solve + fused shift), one DeviceLoop.sens_x0 launch and one
+DeviceLoop.sens_p launch of m = 3 seeded directions over the whole parameter row at the loop's
+resident solution, each with device events, after two warm-up repetitions.  Prints one JSON line per
+shape: medians, min-max spreads, and the ratios sens / solve and sens_p / sens_x0."""
 import json
 import os
 import sys
@@ -40,27 +41,37 @@ def main():
         loop.step()
         loop.step()
         dw, K0, flag = loop.sens_x0()
+        m = 3
+        dP = torch.from_numpy(np.random.default_rng(0).normal(size=(B, m, loop.P.shape[1]))).to(loop.device)
+        dwp, flagp = loop.sens_p(dP)
         its = torch.zeros(B, dtype=torch.int32, device="cuda")
-        solve_ms, sens_ms, it_max = [], [], []
+        solve_ms, sens_ms, sensp_ms, it_max = [], [], [], []
         for rep in range(reps + 2):
-            a, b, c, d = ev(), ev(), ev(), ev()
+            a, b, c, d, e, f = ev(), ev(), ev(), ev(), ev(), ev()
             a.record()
             loop.step(iters_out=its)
             b.record()
             c.record()
             loop.sens_x0(dw_out=dw, K0_out=K0, flag_out=flag)
             d.record()
+            e.record()
+            loop.sens_p(dP, dw_out=dwp, flag_out=flagp)
+            f.record()
             torch.cuda.synchronize()
             if rep >= 2:
                 solve_ms.append(a.elapsed_time(b))
                 sens_ms.append(c.elapsed_time(d))
+                sensp_ms.append(e.elapsed_time(f))
                 it_max.append(int(its.max()))
-        solve_ms, sens_ms = np.array(solve_ms), np.array(sens_ms)
+        solve_ms, sens_ms, sensp_ms = np.array(solve_ms), np.array(sens_ms), np.array(sensp_ms)
         q = lambda v: {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4),  # noqa: E731
                        "max": round(float(v.max()), 4)}
         print(json.dumps({"shape": name, "N": ocp.N, "B": B, "reps": reps, "lockstep_step_ms": q(solve_ms),
                           "sens_x0_ms": q(sens_ms), "ratio_sens_over_step": round(float(np.median(sens_ms) / np.median(solve_ms)), 3),
+                          "sens_p_m": m, "sens_p_ms": q(sensp_ms),
+                          "ratio_sens_p_over_sens_x0": round(float(np.median(sensp_ms) / np.median(sens_ms)), 3),
                           "ipm_iterations_of_the_steps_max": it_max, "irregular": int(flag.sum()),
+                          "irregular_sens_p": int(flagp.sum()),
                           "status_gt1": int((loop.status > 1).sum()), "source_hash": mpcx._lib.source_hash()}), flush=True)
 
 
