@@ -251,8 +251,8 @@ struct DynBicycle {
   // - mu4 vx r + Fyf al(delta) + Fyr be, with
   //   al = -mu3 sin(delta) / m + (mu4 / m + mu5 a / Jz) cos(delta),  be = mu4 / m - mu5 b / Jz,
   // so its gradient and Hessian follow from those of Fyf and Fyr (linear in vy, r and delta,
-  // rational in vx) and of the rotation f0, f1 in psi.  tests/test_ode_cpu.py checks both
-  // against complex steps of f.
+  // rational in vx) and of the rotation f0, f1 in psi.  tests/test_gpu_stage_derivs.py checks
+  // A, B and the Hessian they give, on the device, against a long-double hyper-dual reference.
   static constexpr int kVOff = 2;  // v[0..3] = x[kVOff..kVOff+3]
   struct Cst {
     double im, iJ, a, b, C;
@@ -409,14 +409,18 @@ struct PathBicycle {
   __device__ __forceinline__ static void carry(const S* ue, S* xf) { xf[3] = ue[0]; }
   // reference of the diagonal cost: slot 3 of the row is the curvature, not a reference for s
   __device__ __forceinline__ static double cost_ref(const double* zr, int i) { return i == 3 ? 0.0 : zr[i]; }
-  // w_z (tan(s + d) - L kappa)^2 and its exact derivatives (tan' = 1 + tan^2, tan'' = 2 tan tan')
-  __device__ __forceinline__ static double cost_extra(const double* par, const double* zr, const double* z) {
-    const double r = ::tan(z[3] + z[4]) - par[0] * zr[3];
-    return par[3] * r * r;
+  // acc + w_z (tan(s + d) - L kappa)^2 (acc = the diagonal cost) and the term's exact derivatives
+  // (tan' = 1 + tan^2, tan'' = 2 tan tan').  The residual and the accumulation are explicit fmas:
+  // left to the compiler's contraction, t - L kappa was fused in value() and not in the derivative
+  // pass (where the product L kappa has a second use), and q differed in its last bit between the
+  // line search and the iterate (tests/test_gpu_stage_derivs.py compares the two bit for bit)
+  __device__ __forceinline__ static double cost_extra(const double* par, const double* zr, const double* z, double acc) {
+    const double r = fma(-par[0], zr[3], ::tan(z[3] + z[4]));
+    return fma(par[3] * r, r, acc);
   }
   __device__ __forceinline__ static void cost_extra_derivs(const double* par, const double* zr, const double* z, double fs,
                                                            double* g, double* H) {
-    const double t = ::tan(z[3] + z[4]), t1 = fma(t, t, 1.0), r = t - par[0] * zr[3];
+    const double t = ::tan(z[3] + z[4]), t1 = fma(t, t, 1.0), r = fma(-par[0], zr[3], t);
     const double w2 = 2.0 * fs * par[3];
     const double g1 = w2 * r * t1, h1 = w2 * t1 * fma(2.0 * t, r, t1);  // d/ddelta, d2/ddelta2
     g[3] += g1;
@@ -591,7 +595,7 @@ struct OdeModel {
       const double d = z[i] - ref(c, i);
       acc = fma(wgt(a, i) * d, d, acc);
     }
-    if constexpr (kCostHook) acc += Dyn::cost_extra(a.op.par, c.zr, z);
+    if constexpr (kCostHook) acc = Dyn::cost_extra(a.op.par, c.zr, z, acc);
     return acc;
   }
   template <class Tc>
