@@ -406,6 +406,40 @@ int mpcx_sens_p(mpcx_handle* h, int32_t B, const double* P, const double* w, con
                 const double* lam_x, const double* lbw, const double* ubw, const double* dP, int32_t m, double* dw,
                 int32_t* flag);
 
+/* Adjoint sensitivities (reverse mode of mpcx_sens_p): gP = (dw* / dP)^T g for m cotangents g, each shaped
+ * like a row of w -- the gradient of a scalar loss on the solution with respect to every entry of the
+ * parameter row, x0 and the target or all stage references, from one launch; no solve, no reference
+ * counterpart.  The KKT matrix of mpcx_sens_x0 is symmetric, so the transpose solve is mpcx_sens_p's
+ * Riccati solve of right-hand sides with the same factors and the cotangent in their place:
+ * rq_k = gX_k for k = 0..N (node N included), rr_k = gU_k, d = 0, from a zero start X~_0 = 0, no sign
+ * flipped; then one step of iterative refinement, as mpcx_sens_p.  With its result (X~, U~, p~) and the
+ * costates lam~_k = P_k X~_k + p~_k, for every direction (r_k, d_k, dx0) of mpcx_sens_p
+ *   <g, dw> = lam~_0^T dx0 + sum_{k<N} ( z~_k^T r_k + lam~_{k+1}^T d_k ),   z~_k = (X~_k, U~_k),  lam~_0 = p~_0,
+ * and with r_k = G_k dzr_k, d_k = D_k dzr_k (node costs: G_k = -2 W; D_k = 0 for every supported model)
+ *   gP[:nx] = lam~_0,    gzr_k = G_k^T z~_k + D_k^T lam~_{k+1},
+ *   MPCX_P_X0_STAGEREF:  gP[nx + nz k : nx + nz (k+1)] = gzr_k        (nz = nx + nu)
+ *   MPCX_P_X0_XREF:      gP[nx : 2 nx] = sum_k gzr_k[:nx].
+ * So <g, dw> = <gP, dP> for dw = mpcx_sens_p(dP), to rounding.  Barrier-problem sensitivities, as mpcx_sens_x0.
+ *   gw    B x m x n_w: m cotangents per instance, 1 <= m <= nx per call (more: several calls)
+ *   gP    B x m x n_p: row c of instance b is the gradient for cotangent c; every entry is written (those
+ *         no stage owns as 0).  A cotangent's bits do not depend on the other cotangents or on m, nor an
+ *         instance's on the batch it is in; a zero cotangent gives zeros, and one on the X_0 rows alone
+ *         gives gP[:nx] = gX_0 exactly and zeros elsewhere.
+ *   flag  B: 0 regular, 1 irregular (as mpcx_sens_x0: NaN in all the instance's outputs, the others
+ *         unaffected, the call returns 0).  May be NULL.
+ * Measured against the recursion restated in long double (one MI355X): within 2e-16 relative to
+ * max(1, |entry|) on the linear test problems (tests/test_gpu_sens_vjp.py).
+ * Bounds: as mpcx_sens_x0.  MPCX_EINVAL, with nothing launched: a NULL handle, B <= 0, a NULL pointer
+ * other than lbw / ubw / flag, m outside 1..nx, N >= 64, and MPCX_MODEL_PATH_BICYCLE (its stage rows
+ * enter the dynamics).  The device variant only enqueues one launch on `stream`: it never
+ * synchronises, allocates nothing and can be captured in a graph. */
+int mpcx_sens_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                      const double* d_lam_x, const double* d_gw, int32_t m, double* d_gP, int32_t* d_flag,
+                      void* stream);
+int mpcx_sens_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                  const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m, double* gP,
+                  int32_t* flag);
+
 #ifdef __cplusplus
 }
 #endif

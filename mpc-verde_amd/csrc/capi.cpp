@@ -1025,6 +1025,78 @@ int mpcx_sens_p(mpcx_handle* h, int32_t B, const double* P, const double* w, con
   return 0;
 }
 
+// what both adjoint-sensitivity entry points refuse before anything is launched
+static int check_sens_vjp_args(const mpcx_handle* h, int B, const void* P, const void* w, const void* lam_g,
+                               const void* lam_x, const void* gw, int m, const void* gP) {
+  if (!h) return fail(MPCX_EINVAL, "null handle");
+  if (B <= 0) return fail(MPCX_EINVAL, "sens_vjp: B must be >= 1");
+  if (!P || !w || !lam_g || !lam_x || !gw || !gP)
+    return fail(MPCX_EINVAL, "sens_vjp: P, w, lam_g, lam_x, gw and gP are required");
+  if (m < 1 || m > h->spec.nx) return fail(MPCX_EINVAL, "sens_vjp: m must be between 1 and nx cotangents per call");
+  if (h->spec.N >= 64)
+    return fail(MPCX_EINVAL, "sens_vjp: horizons N >= 64 (lane groups wider than a wavefront) are not supported");
+  if (h->spec.model == MPCX_MODEL_PATH_BICYCLE)
+    return fail(MPCX_EINVAL, "sens_vjp: the path-frame bicycle's stage rows enter its dynamics; not supported");
+  if (int r = check_model_ready(h, B)) return r;
+  return 0;
+}
+
+int mpcx_sens_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                      const double* d_lam_x, const double* d_gw, int32_t m, double* d_gP, int32_t* d_flag,
+                      void* stream) {
+  if (int r = check_sens_vjp_args(h, B, d_P, d_w, d_lam_g, d_lam_x, d_gw, m, d_gP)) return r;
+  if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gP, d_flag, (hipStream_t)stream));
+  return 0;
+}
+
+int mpcx_sens_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                  const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m, double* gP,
+                  int32_t* flag) {
+  if (int r = check_sens_vjp_args(h, B, P, w, lam_g, lam_x, gw, m, gP)) return r;
+  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  if (int r = ensure(h, B)) return r;
+  hipStream_t s = h->stream;
+  const size_t n_gp = (size_t)B * m * h->np, n_gw = (size_t)B * m * h->nw;
+  if (n_gp + n_gw > h->cap_sens) {
+    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
+    dev_free(h->d_sens);
+    h->cap_sens = 0;
+    HIPCHK(hipMalloc(&h->d_sens, (n_gp + n_gw) * sizeof(double)));
+    h->cap_sens = n_gp + n_gw;
+  }
+  int call_xbnd = 0;
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
+  double *d_gp = h->d_sens, *d_gw = h->d_sens + n_gp;
+  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_gw, gw, n_gw * sizeof(double), hipMemcpyHostToDevice, s));
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_vjp(a, h->d_w, h->d_lam, h->d_lamx, d_gw, m, d_gp, h->d_status, s));
+  HIPCHK(hipMemcpyAsync(gP, d_gp, n_gp * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
 int mpcx_rk4_sens_dev(mpcx_handle* h, int32_t B, const double* d_X, const double* d_U, const double* d_xr,
                       double* d_J, void* stream) {
   if (!h || !d_X || !d_U || !d_xr || !d_J) return fail(MPCX_EINVAL, "null argument");

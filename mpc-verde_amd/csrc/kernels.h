@@ -2400,6 +2400,24 @@ static hipError_t launch_sens_p_model(const SolveArgs& a, const double* W, const
   }
 }
 
+// adjoint sensitivities (sens.h sens_vjp_kernel): the same lane groups; m cotangents per instance,
+// 1 <= m <= NX.  No kernel for a model without a reference tangent, as for sens_p.
+template <class Model>
+static hipError_t launch_sens_vjp_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
+                                        const double* GW, int m, double* GP, int32_t* FLAG, hipStream_t stream) {
+  if constexpr (!RefTangentOf<Model>::value) {
+    return hipErrorInvalidValue;
+  } else {
+    if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
+    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+    const int blocks = (int)(((long)a.B * G + 63) / 64);
+    if (G == 16) hipLaunchKernelGGL((sens_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GP, FLAG);
+    else if (G == 32) hipLaunchKernelGGL((sens_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GP, FLAG);
+    else hipLaunchKernelGGL((sens_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GP, FLAG);
+    return hipGetLastError();
+  }
+}
+
 #ifdef MPCX_STAMPS
 // diagnostic build: this unit's setters of its own copies of the stamp/counter pointers
 static int diag_set_stamps(void* d) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_stamps), &d, sizeof(void*)); }
@@ -2428,6 +2446,7 @@ static ModelOps model_ops_of(const char* name) {
 #endif
                   launch_sens_model<Model>,
                   launch_sens_p_model<Model>,
+                  launch_sens_vjp_model<Model>,
   };
 }
 

@@ -121,6 +121,47 @@ struct UnicycleModel {
       }
     }
   }
+  // The transpose of load_ctx (sens.h sens_vjp_kernel): the shared target x_ref, or stage k's own row.
+  __device__ __forceinline__ static RefSlot ref_slot(const ModelArgs& a, int k) {
+    return a.p_layout == 0 ? RefSlot{3, 3, true} : RefSlot{3 + 5 * k, 5, false};
+  }
+  // Reference cotangent of a stage (sens.h sens_vjp_kernel; no solve kernel calls it), the transpose of
+  // ref_tangent: with r = G dzr, d = D dzr (D = 0) its maps, gzr = G^T z~ + D^T lam~ for NX columns at once
+  // (xt: 3 x 3, ut: 2 x 3, gzr: 5 x 3, row = variable, column = cotangent; a column's bits do not depend
+  // on the others).  Node cost: -2 wgt_i z~_i.  Quadrature cost: the columns of G are derivs' gradient at
+  // the unit references minus the one at 0 (ref_tangent's argument: exactly affine), one call site run
+  // six times; a zero cotangent meets only products with 0.
+  __device__ __forceinline__ static void ref_cotangent(const ModelArgs& a, const Ctx&, const double* z, const double* ln,
+                                                       const double* xt, const double* ut, const double*, double* gzr) {
+    if (a.sp.cost != 0) {
+      for (int c = 0; c < 3; ++c) {
+        for (int i = 0; i < 3; ++i) gzr[i * 3 + c] = -2.0 * a.sp.Q[i] * xt[i * 3 + c];
+        for (int i = 0; i < 2; ++i) gzr[(3 + i) * 3 + c] = -2.0 * a.sp.R[i] * ut[i * 3 + c];
+      }
+      return;
+    }
+    double g0[5] = {};
+    for (int i = 0; i < 15; ++i) gzr[i] = 0.0;
+#pragma unroll 1
+    for (int t = 0; t < 6; ++t) {  // t = 0: the references 0; t = j + 1: the unit reference j
+      Ctx rc;
+      for (int i = 0; i < 3; ++i) rc.xr[i] = (t == i + 1) ? 1.0 : 0.0;
+      for (int i = 0; i < 2; ++i) rc.ur[i] = (t == i + 4) ? 1.0 : 0.0;
+      double xf[3], q, A[9], Bm[6], g[5], H[15];
+      derivs(a, rc, z, ln, 1.0, xf, q, A, Bm, g, H);
+      double col[5];  // column t - 1 of G (t = 0: g0 is kept)
+      for (int i = 0; i < 5; ++i) {
+        col[i] = g[i] - g0[i];
+        g0[i] = (t == 0) ? g[i] : g0[i];
+      }
+      for (int c = 0; c < 3; ++c) {
+        double e = col[0] * xt[c];
+        for (int i = 1; i < 3; ++i) e = fma(col[i], xt[i * 3 + c], e);
+        for (int i = 0; i < 2; ++i) e = fma(col[3 + i], ut[i * 3 + c], e);
+        for (int j = 0; j < 5; ++j) gzr[j * 3 + c] = (t == j + 1) ? e : gzr[j * 3 + c];
+      }
+    }
+  }
 };
 
 // The same model for problems without state bounds (configs 1 and 2: X free, |v| <= 1,
@@ -261,6 +302,25 @@ struct LinearModel {
       for (int j = 0; j < NZ; ++j) wi = fma(c.W[symix(i, j, NZ)], dc.zr[j], wi);
       r[i] = -2.0 * wi;
     }
+  }
+  // the transpose of load_ctx: stage k's own references
+  __device__ __forceinline__ static RefSlot ref_slot(const ModelArgs&, int k) {
+    return RefSlot{NX + NZ * k, NZ, false};
+  }
+  // reference cotangent (UnicycleModel::ref_cotangent): gzr = -2 W_j z~ (W symmetric), NX columns
+  __device__ __forceinline__ static void ref_cotangent(const ModelArgs&, const Ctx& c, const double*, const double*,
+                                                       const double* xt, const double* ut, const double*, double* gzr) {
+#pragma unroll
+    for (int i = 0; i < NZ; ++i)
+#pragma unroll
+      for (int col = 0; col < NX; ++col) {
+        double wi = 0.0;
+#pragma unroll
+        for (int j = 0; j < NX; ++j) wi = fma(c.W[symix(i, j, NZ)], xt[j * NX + col], wi);
+#pragma unroll
+        for (int j = 0; j < NU; ++j) wi = fma(c.W[symix(i, NX + j, NZ)], ut[j * NX + col], wi);
+        gzr[i * NX + col] = -2.0 * wi;
+      }
   }
 };
 

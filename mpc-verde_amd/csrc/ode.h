@@ -651,6 +651,20 @@ struct OdeModel {
 #pragma unroll
     for (int i = 0; i < NZ; ++i) r[i] = -2.0 * wgt(a, i) * dc.zr[i];
   }
+  // the transpose of load_ctx (sens.h sens_vjp_kernel): the shared target x_ref, or stage k's own row
+  __device__ __forceinline__ static RefSlot ref_slot(const ModelArgs& a, int k) {
+    return a.p_layout == 0 ? RefSlot{NX, NX, true} : RefSlot{NX + NZ * k, NZ, false};
+  }
+  // reference cotangent (UnicycleModel::ref_cotangent) of the diagonal node cost: gzr_i = -2 wgt_i z~_i,
+  // NX columns (xt: NX x NX, ut: NU x NX, gzr: NZ x NX).  Not for a model with hooks, as ref_tangent.
+  __device__ __forceinline__ static void ref_cotangent(const ModelArgs& a, const Ctx&, const double*, const double*,
+                                                       const double* xt, const double* ut, const double*, double* gzr) {
+    static_assert(!kHooks, "the stage row enters the dynamics: no reference tangent");
+#pragma unroll
+    for (int i = 0; i < NZ; ++i)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) gzr[i * NX + c] = -2.0 * wgt(a, i) * (i < NX ? xt[i * NX + c] : ut[(i - NX) * NX + c]);
+  }
   // Exact derivatives by forward sensitivities and stage adjoints (Dyn::kAdjoint: closed-form
   // partials of f).  Everything in RK4 but f is linear, so with mu_e the adjoint of stage e's f
   // value in lam^T F and Tv_e = dv_e/dz the sensitivity of the variables f reads at stage e,

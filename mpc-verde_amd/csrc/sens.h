@@ -20,7 +20,8 @@
 // same factors as two affine scans -- it takes out the backward sweep's rounding, which an unstable
 // open loop amplifies (the move-blocked cart-pole QP: 1e-13 before, 2e-15 after).
 // The second kernel of the file, sens_p_kernel (below), solves the same system for
-// directions of the whole parameter row: the references and targets beside x0.
+// directions of the whole parameter row: the references and targets beside x0; the third,
+// sens_vjp_kernel, the transpose: the gradient of a loss on w for the whole row.
 // Included by kernels.h.
 #pragma once
 
@@ -790,6 +791,140 @@ __global__ __launch_bounds__(64) void sens_p_kernel(SolveArgs a, const double* _
 #pragma unroll
       for (int c = 0; c < NX; ++c)
         if (c < m) dw[(size_t)iuw<NX, NU>(k, l) * m + c] = regular ? U[l * NX + c] : nan;
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Adjoint sensitivities: gP = (dw*/dP)^T g for up to NX cotangents g per launch, each shaped like w
+// (DESIGN.md §3.5.2).  The KKT matrix is symmetric, so the transpose solve is sens_p_kernel's Riccati
+// solve of right-hand sides with the cotangent in their place: rq_k = gX_k on every node (node N
+// included), rr_k = gU_k, d = 0, from a zero start X~_0 = 0 -- no sign is flipped.  With its result
+// (X~, U~, p~) and the costates lam~_k = P_k X~_k + p~_k, for every direction (r_k, d_k, dx0) of sens_p
+//   <g, dw> = lam~_0^T dx0 + sum_{k<N} (z~_k^T r_k + lam~_{k+1}^T d_k),     z~_k = (X~_k, U~_k),
+// and with r_k = G_k dzr_k, d_k = D_k dzr_k the model's reference tangent as matrices the gradient row is
+//   gP[:nx] = lam~_0,     gzr_k = G_k^T z~_k + D_k^T lam~_{k+1}  (Model::ref_cotangent),
+// placed in the row by the transpose of load_ctx's row -> stage mapping (Model::ref_slot): stage k's own
+// entries, or one shared target on which the stages' terms are summed over the lane group.
+// W, LG, LX: the point, as for sens_kernel; GW: B x m x nw cotangents; GP: B x m x p_stride, every entry
+// written (those no stage owns as 0); FLAG: B or null (sens_kernel's).  1 <= m <= NX.
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_vjp_kernel(SolveArgs a, const double* __restrict__ W,
+                                                      const double* __restrict__ LG, const double* __restrict__ LX,
+                                                      const double* __restrict__ GW, int m, double* __restrict__ GP,
+                                                      int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+
+  // ---- right-hand sides, one column per cotangent: its rows of my node (node N has its X rows too)
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double gx[NX] = {}, gu[NU] = {};
+    if (c < m) {  // (launch-uniform)
+      const double* gw = GW + ((size_t)(valid ? inst : 0) * m + c) * nw;
+      if (hasX)
+        for (int i = 0; i < NX; ++i) gx[i] = gw[ixw<NX, NU>(k, i)];
+      if (hasU)
+        for (int l = 0; l < NU; ++l) gu[l] = gw[iuw<NX, NU>(k, l)];
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      Rq[i * NX + c] = gx[i];
+      Dd[i * NX + c] = 0.0;
+      X[i * NX + c] = 0.0;
+      pk[i * NX + c] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      Rr[l * NX + c] = gu[l];
+      U[l * NX + c] = 0.0;
+    }
+  }
+
+  // ---- the Riccati solve of the right-hand sides and one step of iterative refinement, as sens_p_kernel
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  // ---- costates lam~_k = P_k X~_k + p~_k (sens_refine's own), lam~_{k+1} from the next lane
+  double lamk[NN], Ln[NN];
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      double e = s.P[symix(i, 0, NX)] * X[c];
+#pragma unroll
+      for (int mm = 1; mm < NX; ++mm) e = fma(s.P[symix(i, mm, NX)], X[mm * NX + c], e);
+      e += pk[i * NX + c];
+      lamk[i * NX + c] = hasX ? e : 0.0;
+    }
+#pragma unroll
+  for (int i = 0; i < NN; ++i) {
+    const double ln = from_next(lamk[i]);
+    Ln[i] = hasU ? ln : 0.0;
+  }
+
+  // ---- regular: as sens_kernel
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]) + fabs(lamk[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  // ---- contraction with the reference tangent: gzr_k = G_k^T z~_k + D_k^T lam~_{k+1}, all columns
+  double gzr[NZ * NX];
+  Model::ref_cotangent(ma, s.ctx, s.ze, s.ln, X, U, Ln, gzr);
+#pragma unroll
+  for (int i = 0; i < NZ * NX; ++i) gzr[i] = hasU ? gzr[i] : 0.0;
+  const RefSlot slot = Model::ref_slot(ma, k);  // (shared: launch-uniform)
+  if (slot.shared)  // every lane ends with the same bits (the symmetric reduction of collectives.h)
+#pragma unroll
+    for (int i = 0; i < NZ * NX; ++i) gzr[i] = gsum<G>(gzr[i], xw);
+
+  const int np = a.p_stride;
+  const bool mine = slot.shared ? (valid && k == 0) : hasU;  // who writes the references' entries
+  const int tail = slot.shared ? slot.off + slot.n : NX + NZ * N;  // the row's entries past the owned ones
+  const bool tails = valid && k == (slot.shared ? 0 : N);
+#pragma unroll
+  for (int c = 0; c < NX; ++c)
+    if (c < m) {
+      double* gp = GP + ((size_t)(valid ? inst : 0) * m + c) * np;
+      if (valid && k == 0)
+        for (int i = 0; i < NX; ++i) gp[i] = regular ? lamk[i * NX + c] : nan;
+      if (mine)
+#pragma unroll
+        for (int i = 0; i < NZ; ++i)
+          if (i < slot.n) gp[slot.off + i] = regular ? gzr[i * NX + c] : nan;
+      if (tails)
+        for (int j = tail; j < np; ++j) gp[j] = regular ? 0.0 : nan;
+    }
   if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
 }
 

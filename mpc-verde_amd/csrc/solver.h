@@ -101,6 +101,14 @@ struct ModelArgs {
 };
 __host__ __device__ inline ModelArgs model_args(const SolveArgs& a) { return ModelArgs{a.sp, a.lin, a.op, a.p_layout, a.N}; }
 
+// The transpose of a model's load_ctx (Model::ref_slot, beside it): where the gradient with respect to
+// stage k's references lands in a row of P -- its first n entries at P[off .. off + n) -- and whether that
+// is one target shared by all stages (their gradients are summed there) or the stage's own entries.
+struct RefSlot {
+  int off, n;
+  bool shared;
+};
+
 // lane group of the solve launch: the smallest power of two holding nodes 0..N; a batch too
 // small to give every SIMD a wave gets wider groups (up to one instance per wave) unless
 // group_policy = 1.  G > 64 spans G/64 waves (one workgroup per instance).
@@ -183,6 +191,10 @@ struct ModelOps {
   // (B x m x p_stride) directions shaped like rows of P, 1 <= m <= nx; DW (B x nw x m); FLAG as above
   hipError_t (*sens_p)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* DP, int m,
                        double* DW, int32_t* FLAG, hipStream_t stream);
+  // adjoint sensitivities at the same point (sens.h sens_vjp_kernel): GW (B x m x nw) cotangents shaped
+  // like w, 1 <= m <= nx; GP (B x m x p_stride) gradient rows shaped like P, every entry written; FLAG as above
+  hipError_t (*sens_vjp)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* GW,
+                         int m, double* GP, int32_t* FLAG, hipStream_t stream);
   // doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
   int ws_slots() const { return !resto ? 0 : RestoWs::slots(nx, nu) + (ws_stash ? chain_ws_slots(nx, nu) : 0); }
 };

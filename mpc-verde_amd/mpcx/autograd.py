@@ -1,0 +1,76 @@
+"""The batched MPC solve as a differentiable PyTorch function (reverse mode).
+
+``solve_differentiable(loop, P)`` solves the loop's B problems at the parameter rows P and returns
+the solutions w (B, n_w) as a tensor that carries a backward: for a scalar loss L(w), ``P.grad`` is
+(dw*/dP)^T dL/dw, from ONE adjoint-sensitivity launch (``DeviceLoop.sens_vjp``, mpcx_sens_vjp_dev) on
+the loop's stream -- no solve, no host synchronisation, every entry of the row at once::
+
+    loop = DeviceLoop(solver, P0)
+    P = torch.tensor(P0, device="cuda", requires_grad=True)
+    w = solve_differentiable(loop, P)
+    loss = 0.5 * ((w[:, nx:nx + nu] - u_target) ** 2).sum()      # imitation loss on the first move
+    loss.backward()                                              # P.grad: (B, n_p)
+
+PyTorch provides the tensors, streams and the autograd graph only; the arithmetic is libmpcx's HIP
+kernels.  Layouts are the kernel's, as for the other ``DeviceLoop`` methods (a padded linear model:
+its pad entries included).  These are the sensitivities of the barrier problem at the returned
+multipliers (include/mpcx.h, mpcx_sens_x0).
+"""
+from __future__ import annotations
+
+import torch
+
+from .device import DeviceLoop
+
+__all__ = ["MPCFunction", "solve_differentiable"]
+
+
+class MPCFunction(torch.autograd.Function):
+    """forward(P, loop, zero_irregular): copies P into the loop, enqueues ``loop.solve()`` and returns a
+    copy of w; the point (P, w, lam, lamx) is saved as copies, so later solves of the same loop do not
+    move it.  backward: one ``loop.sens_vjp`` launch at the saved point with dL/dw as the cotangent."""
+
+    @staticmethod
+    def forward(ctx, P, loop, zero_irregular):
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)  # (device-side ordering only: nothing waits on the host)
+        with torch.cuda.stream(loop.stream):
+            loop.P.copy_(P.detach(), non_blocking=True)
+            loop.solve()
+            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
+            w = point[1].clone()
+        cur.wait_stream(loop.stream)
+        ctx.loop, ctx.zero_irregular = loop, zero_irregular
+        ctx.save_for_backward(*point)
+        return w
+
+    @staticmethod
+    def backward(ctx, gw):
+        loop = ctx.loop
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)
+        with torch.cuda.stream(loop.stream):
+            g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
+            gP, flag = loop.sens_vjp(g, point=ctx.saved_tensors)
+            gP = gP[:, 0]
+            if ctx.zero_irregular:
+                gP = torch.where(flag[:, None] != 0, torch.zeros_like(gP), gP)
+        cur.wait_stream(loop.stream)
+        return gP, None, None
+
+
+def solve_differentiable(loop: DeviceLoop, P, irregular="nan"):
+    """Solve the loop's problems at P (B, n_p float64 device tensor, the loop's resident layout) and
+    return w (B, n_w) with the backward described above.  The loop is used as it stands: its warm
+    start is the one its next ``solve()`` would take, and its resident P, w, lam, lamx, status and
+    iters are this solve's afterwards.
+
+    irregular: what an instance flagged irregular (a variable on its bound, an indefinite reduced
+    Hessian) contributes to ``P.grad`` -- "nan" (default: its row is NaN, the others are unaffected)
+    or "zero" (its row is replaced by zeros)."""
+    if irregular not in ("nan", "zero"):
+        raise ValueError('irregular: "nan" or "zero"')
+    if not isinstance(P, torch.Tensor) or P.dtype != torch.float64 or tuple(P.shape) != tuple(loop.P.shape) \
+            or P.device != loop.device:
+        raise ValueError(f"P: expected a float64 tensor of shape {tuple(loop.P.shape)} on {loop.device}")
+    return MPCFunction.apply(P, loop, irregular == "zero")

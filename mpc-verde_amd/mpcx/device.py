@@ -151,6 +151,36 @@ class DeviceLoop:
                                                ctypes_void(self.stream.cuda_stream)))
         return dw, flag
 
+    def sens_vjp(self, gw, gP_out=None, flag_out=None, point=None):
+        """Enqueue one adjoint-sensitivity launch (mpcx_sens_vjp_dev) at the loop's resident P, w, lam,
+        lamx: gw (B, m, n_w) float64 device tensor of m <= nx cotangents, each shaped like a row of the
+        resident w (the kernel's layout: a padded linear model's pad entries included), gives
+        gP (B, m, n_p) = (dw/dP)^T gw, the gradient rows shaped like the resident P, and flag (B,) int32
+        (1 = irregular instance, NaN outputs).  point = (P, w, lam, lamx): device tensors of the
+        resident ones' shapes to take the point from instead (the next solve overwrites the resident
+        ones; a saved point does not move).  Tensors given are written in place, the others are
+        allocated; returns (gP, flag) without waiting for the stream."""
+        nw, nx, n_p, ng = self.solver._h.n_w, self._knx, self.P.shape[1], self.lam.shape[1]
+        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
+            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
+        m = gw.shape[1]
+        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
+        if point is None:
+            point = (self.P, self.w, self.lam, self.lamx)
+        elif len(point) != 4:
+            raise ValueError("point: expected (P, w, lam, lamx)")
+        for t, name, n in zip(point, ("point P", "point w", "point lam", "point lamx"), (n_p, nw, ng, nw)):
+            _check(t, name, torch.float64, (self.B, n), self.device)
+        with torch.cuda.stream(self.stream):
+            gP = torch.empty((self.B, m, n_p), dtype=torch.float64, device=self.device) if gP_out is None else gP_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        _check(gP, "gP_out", torch.float64, (self.B, m, n_p), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
+                                                 _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gP), _ptr(flag),
+                                                 ctypes_void(self.stream.cuda_stream)))
+        return gP, flag
+
     def set_stage_refs(self, refs):
         """Per-step stage references (tracking, param layout x0_stageref): refs is a
         (B, N*(nx+nu)) float64 device tensor copied into P[:, nx:] on the loop's stream

@@ -334,6 +334,78 @@ class Solver:
         s = self.sens_p(P, res, dP, lbw, ubw)
         return {"dw_dxref": s["dw"], "Kr": s["du0"], "flag": s["flag"]}
 
+    def sens_vjp(self, P, res, gw, lbw=None, ubw=None):
+        """Adjoint sensitivities of the solutions ``res`` (mpcx_sens_vjp): gP = (d w*/d P)^T gw, the
+        gradient with respect to every entry of the parameter row of a scalar loss whose gradient on the
+        solution w is gw -- reverse mode of :meth:`sens_p`, no solve: <gw, sens_p(dP)> = <gP, dP>.
+
+        gw: (B, m, n_w) cotangents, each shaped like a row of w, or (B, n_w) for a single one; any m
+        (launches of at most nx columns each; a cotangent's bits do not depend on the others).  The
+        single-shooting form takes them over its own w, the control rows.
+        lbw / ubw: as for :meth:`sens_x0`.
+        Returns {'gP': (B, m, n_p), 'flag': (B,)}; flag 1 marks an irregular instance (NaN outputs), as
+        :meth:`sens_x0`.  Not for the path-frame bicycle (its stage rows enter the dynamics)."""
+        P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
+        B = P.shape[0]
+        if P.shape[1] != self.n_p:
+            raise ValueError(f"P: expected {self.n_p} columns, got {P.shape[1]}")
+        nw, ng = self._ms_nw, self._ms_ng
+        nx, nu = self.ocp.nx, self.ocp.nu
+        single = self.ocp.formulation == "single_shooting"
+        n_gw = self.ocp.N * nu if single else nw
+        gw = np.asarray(gw, np.float64)
+        if gw.ndim == 2:
+            gw = gw[:, None, :]
+        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != n_gw or gw.shape[1] < 1:
+            raise ValueError(f"gw: expected ({B}, m, {n_gw}) or ({B}, {n_gw}), got {gw.shape}")
+        m = gw.shape[1]
+        if single:  # the control rows of a zero row of w
+            nz = nx + nu
+            full = np.zeros((B, m, nw))
+            full[:, :, np.concatenate([nx + nz * k + np.arange(nu) for k in range(self.ocp.N)])] = gw
+            gw = full
+        w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
+                        for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
+        lbw, ubw = _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw")
+        knx, n_p = nx, self.n_p
+        pd = self._pad
+        if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
+            P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
+            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
+            w, lamx = pd.scatter(w, pd.w_idx, pd.n_w_pad), pd.scatter(lamx, pd.w_idx, pd.n_w_pad)
+            lam = pd.scatter(lam, pd.g_idx, pd.n_g_pad)
+            lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
+            ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
+            knx, n_p = pd.nxp, pd.n_p_pad
+        gP = np.empty((B, m, n_p))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+        for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
+            mc = min(knx, m - c0)
+            part, fl = np.empty((B, mc, n_p)), np.empty(B, np.int32)
+            gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
+            _lib.check(lib.mpcx_sens_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam), _lib.dptr(lamx),
+                                         _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(gwc), mc, _lib.dptr(part),
+                                         _lib.iptr(fl)))
+            gP[:, c0:c0 + mc] = part
+            flag |= fl
+        if pd is not None:  # the model's own parameters only
+            gP = gP[:, :, pd.p_idx]
+        return {"gP": np.ascontiguousarray(gP), "flag": flag}
+
+    def gain_p(self, P, res, lbw=None, ubw=None):
+        """The first move's gain on every parameter, dU_0/dP, from one launch (:meth:`sens_vjp` with the
+        nu unit cotangents on the rows of U_0).  Returns {'dU0_dP': (B, nu, n_p), 'flag': (B,)}: its
+        x0 block is :meth:`sens_x0`'s K0, and on the x0_xref layout its x_ref block is :meth:`sens_xref`'s
+        Kr, each to rounding: u ~ u0* + dU0_dP (P' - P)."""
+        nx, nu = self.ocp.nx, self.ocp.nu
+        B = np.atleast_2d(np.asarray(P)).shape[0]
+        single = self.ocp.formulation == "single_shooting"
+        gw = np.zeros((B, nu, self.ocp.N * nu if single else self._ms_nw))
+        gw[:, np.arange(nu), (0 if single else nx) + np.arange(nu)] = 1.0
+        s = self.sens_vjp(P, res, gw, lbw, ubw)
+        return {"dU0_dP": s["gP"], "flag": s["flag"]}
+
     def rk4_sens(self, w, P):
         """Per-interval defects, costs and Jacobians at w (B, n_w) -- the sweep kernel."""
         if self.ocp.model != "unicycle":

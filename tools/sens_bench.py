@@ -1,13 +1,14 @@
-"""Time of one sensitivity launch (mpcx_sens_x0_dev, mpcx_sens_p_dev) next to one lock-step solve of the same batch.
+"""Time of one sensitivity launch (mpcx_sens_x0_dev, mpcx_sens_p_dev, mpcx_sens_vjp_dev) next to one lock-step solve of the same batch.
 
     python tools/sens_bench.py [B] [reps]      (defaults 1024, 9)
 
 Two shapes: config 2 (unicycle point-to-point, N = 20) and the cart-pole QP at N = 50.  Each batch
 is stepped twice (a cold and a warm closed-loop step), then every repetition times one warm
-lock-step step (DeviceLoop.step: solve + fused shift), one DeviceLoop.sens_x0 launch and one
-DeviceLoop.sens_p launch of m = 3 seeded directions over the whole parameter row at the loop's
+lock-step step (DeviceLoop.step: solve + fused shift), one DeviceLoop.sens_x0 launch, one
+DeviceLoop.sens_p launch of m = 3 seeded directions over the whole parameter row and one
+DeviceLoop.sens_vjp launch of m = 3 and of m = 1 seeded cotangents over the whole of w at the loop's
 resident solution, each with device events, after two warm-up repetitions.  Prints one JSON line per
-shape: medians, min-max spreads, and the ratios sens / solve and sens_p / sens_x0."""
+shape: medians, min-max spreads, and the ratios sens / solve, sens_p / sens_x0 and sens_vjp / sens_p."""
 import json
 import os
 import sys
@@ -44,8 +45,12 @@ def main():
         m = 3
         dP = torch.from_numpy(np.random.default_rng(0).normal(size=(B, m, loop.P.shape[1]))).to(loop.device)
         dwp, flagp = loop.sens_p(dP)
+        gw = torch.from_numpy(np.random.default_rng(1).normal(size=(B, m, loop.w.shape[1]))).to(loop.device)
+        gw1 = gw[:, :1].contiguous()
+        gP, flagv = loop.sens_vjp(gw)
+        gP1, _ = loop.sens_vjp(gw1)
         its = torch.zeros(B, dtype=torch.int32, device="cuda")
-        solve_ms, sens_ms, sensp_ms, it_max = [], [], [], []
+        solve_ms, sens_ms, sensp_ms, vjp_ms, vjp1_ms, it_max = [], [], [], [], [], []
         for rep in range(reps + 2):
             a, b, c, d, e, f = ev(), ev(), ev(), ev(), ev(), ev()
             a.record()
@@ -57,19 +62,32 @@ def main():
             e.record()
             loop.sens_p(dP, dw_out=dwp, flag_out=flagp)
             f.record()
+            g, h, i, j = ev(), ev(), ev(), ev()
+            g.record()
+            loop.sens_vjp(gw, gP_out=gP, flag_out=flagv)
+            h.record()
+            i.record()
+            loop.sens_vjp(gw1, gP_out=gP1, flag_out=flagv)
+            j.record()
             torch.cuda.synchronize()
             if rep >= 2:
                 solve_ms.append(a.elapsed_time(b))
                 sens_ms.append(c.elapsed_time(d))
                 sensp_ms.append(e.elapsed_time(f))
+                vjp_ms.append(g.elapsed_time(h))
+                vjp1_ms.append(i.elapsed_time(j))
                 it_max.append(int(its.max()))
         solve_ms, sens_ms, sensp_ms = np.array(solve_ms), np.array(sens_ms), np.array(sensp_ms)
+        vjp_ms, vjp1_ms = np.array(vjp_ms), np.array(vjp1_ms)
         q = lambda v: {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4),  # noqa: E731
                        "max": round(float(v.max()), 4)}
         print(json.dumps({"shape": name, "N": ocp.N, "B": B, "reps": reps, "lockstep_step_ms": q(solve_ms),
                           "sens_x0_ms": q(sens_ms), "ratio_sens_over_step": round(float(np.median(sens_ms) / np.median(solve_ms)), 3),
                           "sens_p_m": m, "sens_p_ms": q(sensp_ms),
                           "ratio_sens_p_over_sens_x0": round(float(np.median(sensp_ms) / np.median(sens_ms)), 3),
+                          "sens_vjp_m": m, "sens_vjp_ms": q(vjp_ms), "sens_vjp_m1_ms": q(vjp1_ms),
+                          "ratio_sens_vjp_over_sens_p": round(float(np.median(vjp_ms) / np.median(sensp_ms)), 3),
+                          "irregular_sens_vjp": int(flagv.sum()),
                           "ipm_iterations_of_the_steps_max": it_max, "irregular": int(flag.sum()),
                           "irregular_sens_p": int(flagp.sum()),
                           "status_gt1": int((loop.status > 1).sum()), "source_hash": mpcx._lib.source_hash()}), flush=True)
