@@ -51,6 +51,11 @@ __device__ __forceinline__ Pair halves32(double v) {
 // v_min_f64.  LLVM's fmax/fmin must first quiet each operand it cannot prove quiet (a
 // `v_max_f64 x, x` per DPP-moved, loaded or |.|-modified operand: 229 of the config-2 kernel's
 // 404 v_max_f64); the instruction's result for quiet NaNs and numbers is the same.
+// Pinned on the device (tests/test_gpu_collectives.py): they are np.fmax / np.fmin -- a quiet NaN
+// operand is DROPPED (the other operand comes back; NaN only when both are), so a max or a gmax /
+// gmin never reports a NaN and anything that must notice one needs a sum (kernels.h, the
+// termination test's `tot`); of (+0, -0) in either order max returns +0 and min -0, so group
+// results are lane-uniform in the sign of zero too (gsum of mixed zeros is +0).
 __device__ __forceinline__ double qmax(double a, double b) {
   double r;
   asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -323,8 +328,30 @@ __device__ __forceinline__ void matvec_bcast(double* acc, const double* w, doubl
   }
 }
 
-// 1/x to full fp64 accuracy: v_rcp_f64 + two Newton steps (no IEEE division sequence
-// on the sequential critical path)
+// 1/x: v_rcp_f64 + two Newton steps (no IEEE division sequence on the sequential critical path).
+// Accuracy (tests/test_gpu_collectives.py, one MI355X): over 100160 arguments of both signs,
+// log-uniform in 2^-1021 <= |x| <= 2^1021 plus powers of two, their neighbours, 3, 1/3 and the
+// largest mantissa, the maximum error is 0.5000 ulp and 100.000 % of the results are the correctly
+// rounded reciprocal (asserted: <= 1 ulp -- the last fma rounds once on a residual far below 1/2 ulp).
+// Domain: every x with a finite nonzero reciprocal that was tried beyond that range -- subnormal x
+// down to 1.25 * 2^-1024, |x| up to DBL_MAX with subnormal results -- also came out correctly
+// rounded.  Outside it the result is NaN, never +-inf or +-0: +-0 and +-inf (fma(-x, r, 1) is
+// 0 * inf), NaN, and |x| <= 2^-1024, where v_rcp_f64 overflows to inf and the steps make it NaN.
+// Call sites that can see such an argument, and what catches it:
+//  * Riccati pivots (riccati.h riccati_step / dec_prefactor, rowchain.h, rowchain6.h, pscan.h
+//    relem_stage): a zero, negative or NaN pivot fails the step's own test (d0 > 0, det > 0) or
+//    fac_ok (r0 > 0 && r0 < INFINITY, false for NaN: a NaN pivot is read as indefinite) and goes to
+//    the inertia correction; a positive pivot below 2^-1024 gives NaN factors where IEEE division
+//    would give inf -- fac_ok rejects both alike.
+//  * pscan.h inv_nopiv (no pivoting): a zero pivot makes the element NaN; the scan's self-check
+//    (backward.h: tot < INFINITY on a sum) rejects the scan and the sequential sweep runs.
+//  * slacks z - lb, ub - z (kernels.h, resto.h): positive by the fraction-to-boundary rule and the
+//    bound push; a NaN iterate gives NaN here and is stopped by the termination test's finiteness term.
+//  * rcp64(dz), rcp64(dzL), rcp64(dzU) in the fraction-to-boundary step: a zero or NaN step gives
+//    NaN, but the value is only used under dz < 0 / dz > 0 / dzL < 0, false in both cases.
+//  * fastmath.h: 2 + f and 2 - c lie in [1, 3] for finite arguments (log_fd / exp_fd treat the
+//    special values by selects and clamps).
+// No call site relies on +-inf or +-0 coming back.
 __device__ __forceinline__ double rcp64(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = fma(-x, r, 1.0);

@@ -968,9 +968,23 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
     // acceptable_* and the objective change from the previous iterate) for acceptable_iter
     // iterates in a row.  fcur = the scaled objective.
     const double fcur = fs * sums[2];
+    // A max drops a quiet NaN (v_max_f64 and fmax return the other operand): a NaN residual leaves
+    // Ed / Ec at 0 and would pass every threshold above -- a NaN reference, multiplier or iterate
+    // ended as "converged" at a feasible, complementary start.  A sum cannot swallow one: a NaN or
+    // an infinity in any residual or in the objective makes tot NaN or infinite (every entry of z,
+    // lam, zL, zU enters rd, cdef or c0 on some lane of the group).  Joined into both tests, so the
+    // acceptable point at a failed line search and the restoration's use of it are covered; for
+    // finite data the term is true and no decision moves (tests/test_gpu_nonfinite.py).
+    double tot = fcur;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) tot += rd[i];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) tot += cdef[i] + c0[i];
+    const bool fin = fabs(tot) < INFINITY;
     bool conv_g, acc_g;
-    group_tests2(E0 <= a.tol && Ed <= a.dual_inf_tol * fs && Ec <= a.constr_viol_tol && Ecomp0 <= a.compl_inf_tol * fs,
-                 E0 <= a.acc_tol && Ed <= a.acc_dual_inf_tol * fs && Ec <= a.acc_constr_viol_tol &&
+    group_tests2(fin && E0 <= a.tol && Ed <= a.dual_inf_tol * fs && Ec <= a.constr_viol_tol &&
+                     Ecomp0 <= a.compl_inf_tol * fs,
+                 fin && E0 <= a.acc_tol && Ed <= a.acc_dual_inf_tol * fs && Ec <= a.acc_constr_viol_tol &&
                      Ecomp0 <= a.acc_compl_inf_tol * fs,
                  conv_g, acc_g);
     const bool acceptable_now = acc_g && fabs(fcur - f_last) <= a.acc_obj_change_tol * fmax(1.0, fabs(fcur));

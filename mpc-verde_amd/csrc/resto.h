@@ -569,7 +569,18 @@ __device__ __forceinline__ void recover(RecIO& io, FilterLds<G>& filt, const Mod
     z1 = gsum<G>(z1, xw);
     const double sd = fmax(kSmax, (lam1 + z1) / ((double)io.ng + nvar)) / kSmax;
     const double sc = fmax(kSmax, nbnd > 0 ? z1 / nbnd : 0.0) / kSmax;
-    if (fmax(fmax(Ed / sd, Ec), Ecomp / sc) <= io.tol) {  // converged to a point of local infeasibility
+    // (fmax drops a NaN -- kernels.h, the termination test: the sum keeps it, and a non-finite
+    //  restoration iterate is not a point of local infeasibility)
+    double tot = 0;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) tot += rd[i];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      if (hasU) tot += (cdef[i] - p1[i] + n1[i]) + (ln[i] + zp1[i] + zn1[i]);
+      if (has0) tot += (c0[i] - p0[i] + n0[i]) + (lam[i] + zp0[i] + zn0[i]);
+    }
+    const bool fin = fabs(gsum<G>(tot, xw)) < INFINITY;
+    if (fin && fmax(fmax(Ed / sd, Ec), Ecomp / sc) <= io.tol) {  // converged to a point of local infeasibility
       io.status = 4;
       io.its = itr;
       write_back();
