@@ -440,6 +440,55 @@ int mpcx_sens_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, c
                   const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m, double* gP,
                   int32_t* flag);
 
+/* Directional sensitivities of the solution to the box bounds lbw / ubw at a primal-dual point as a solve
+ * returns it: dw = (dw* / dlbw) dlbw + (dw* / dubw) dubw for m pairs of directions, each shaped like w.
+ * One launch, no solve, every model (MPCX_MODEL_PATH_BICYCLE included: no reference hook of the model is
+ * involved); no reference counterpart -- it replaces central differences of whole solves under moved
+ * bounds.  With the complementarity products zL_i (w_i - lbw_i) and zU_i (ubw_i - w_i) held fixed the
+ * KKT matrix is that of mpcx_sens_x0 and the bounds enter the right-hand side alone,
+ *   r_i = -(sigL_i dlbw_i + sigU_i dubw_i),  sigL_i = zL_i / (w_i - lbw_i),  sigU_i = zU_i / (ubw_i - w_i),
+ * on every finitely bounded variable, the X rows of node N included; d_k = 0 and dX_0 = 0.  The solve is
+ * mpcx_sens_p's (Riccati solve of right-hand sides, one step of iterative refinement).
+ * zL = max(-lam_x, 0), zU = max(lam_x, 0) is the ONE-SIDED split of the returned multiplier zU - zL that
+ * Sigma of mpcx_sens_x0 uses: at most one of sigL_i, sigU_i is non-zero.  On a two-sided box the far
+ * side's own multiplier mu / slack is dropped: an O(mu) error at the solver's final mu (1e-9), like the
+ * difference between barrier and active-set sensitivities, but 2.6e-2 at mu = 1e-3 in a CPU check where
+ * the exact split gave 3e-10.  At a strictly active bound dw_i -> dbound_i; at an inactive one the effect
+ * is O(mu).
+ *   dlbw, dubw  B x m x n_w each, 1 <= m <= nx per call; entries on X_0's rows and where the bound lies
+ *               beyond +-1e19 are ignored (not read)
+ *   dw          B x n_w x m, mpcx_sens_p's layout (the X_0 rows are exact zeros).  A column's bits do not
+ *               depend on the other columns or on m, nor an instance's on the batch it is in.
+ *   flag        as mpcx_sens_p.
+ * Bounds in force: as mpcx_sens_x0.  MPCX_EINVAL, with nothing launched: a NULL handle, B <= 0, a NULL
+ * pointer other than lbw / ubw / flag, m outside 1..nx, N >= 64.  The device variant only enqueues one
+ * launch on `stream`: it never synchronises, allocates nothing and can be captured in a graph. */
+int mpcx_sens_bounds_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                         const double* d_lam_x, const double* d_dlbw, const double* d_dubw, int32_t m, double* d_dw,
+                         int32_t* d_flag, void* stream);
+int mpcx_sens_bounds(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                     const double* lam_x, const double* lbw, const double* ubw, const double* dlbw,
+                     const double* dubw, int32_t m, double* dw, int32_t* flag);
+
+/* Reverse mode of mpcx_sens_bounds: the gradients of a scalar loss on the solution with respect to every
+ * entry of lbw and ubw, for m cotangents g shaped like w, from one launch; no reference counterpart (it
+ * replaces 2 n_w finite-difference solves).  With z~ = (X~, U~) the adjoint solve of mpcx_sens_vjp
+ * (rq_k = gX_k on every node, rr_k = gU_k, zero start, one refinement step),
+ *   glbw_i = -sigL_i z~_i,   gubw_i = -sigU_i z~_i      (sigL, sigU: the one-sided split above),
+ * so <g, dw> = <glbw, dlbw> + <gubw, dubw> for dw = mpcx_sens_bounds(dlbw, dubw), to rounding.
+ *   gw          B x m x n_w, 1 <= m <= nx per call
+ *   glbw, gubw  B x m x n_w each; every entry is written: 0 on X_0's rows and where there is no finite
+ *               bound, NaN throughout for an irregular instance.  A cotangent's bits do not depend on the
+ *               others or on m, nor an instance's on its batch; a zero cotangent gives zeros.
+ *   flag        as mpcx_sens_p.
+ * Bounds, refusals and the device variant: as mpcx_sens_bounds. */
+int mpcx_sens_bounds_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                             const double* d_lam_x, const double* d_gw, int32_t m, double* d_glbw, double* d_gubw,
+                             int32_t* d_flag, void* stream);
+int mpcx_sens_bounds_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                         const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
+                         double* glbw, double* gubw, int32_t* flag);
+
 #ifdef __cplusplus
 }
 #endif

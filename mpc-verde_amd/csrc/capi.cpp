@@ -1097,6 +1097,136 @@ int mpcx_sens_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, c
   return 0;
 }
 
+// what the four bound-sensitivity entry points refuse before anything is launched (every model is
+// accepted: the right-hand sides come from Sigma, no reference hook of the model)
+static int check_sens_bounds_args(const mpcx_handle* h, int B, const char* who, bool ptrs, int m) {
+  auto say = [&](const char* what) { return fail(MPCX_EINVAL, std::string(who) + ": " + what); };
+  if (!h) return fail(MPCX_EINVAL, "null handle");
+  if (B <= 0) return say("B must be >= 1");
+  if (!ptrs) return say("P, w, lam_g, lam_x, the directions or cotangents and the outputs are required");
+  if (m < 1 || m > h->spec.nx) return say("m must be between 1 and nx columns per call");
+  if (h->spec.N >= 64) return say("horizons N >= 64 (lane groups wider than a wavefront) are not supported");
+  if (int r = check_model_ready(h, B)) return r;
+  return 0;
+}
+
+int mpcx_sens_bounds_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                         const double* d_lam_x, const double* d_dlbw, const double* d_dubw, int32_t m, double* d_dw,
+                         int32_t* d_flag, void* stream) {
+  if (int r = check_sens_bounds_args(h, B, "sens_bounds", d_P && d_w && d_lam_g && d_lam_x && d_dlbw && d_dubw && d_dw, m))
+    return r;
+  if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_bnd(a, d_w, d_lam_g, d_lam_x, d_dlbw, d_dubw, m, d_dw, d_flag, (hipStream_t)stream));
+  return 0;
+}
+
+int mpcx_sens_bounds(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                     const double* lam_x, const double* lbw, const double* ubw, const double* dlbw,
+                     const double* dubw, int32_t m, double* dw, int32_t* flag) {
+  if (int r = check_sens_bounds_args(h, B, "sens_bounds", P && w && lam_g && lam_x && dlbw && dubw && dw, m)) return r;
+  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  if (int r = ensure(h, B)) return r;
+  hipStream_t s = h->stream;
+  const size_t n_dw = (size_t)B * h->nw * m, n_d = (size_t)B * m * h->nw;
+  if (n_dw + 2 * n_d > h->cap_sens) {
+    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
+    dev_free(h->d_sens);
+    h->cap_sens = 0;
+    HIPCHK(hipMalloc(&h->d_sens, (n_dw + 2 * n_d) * sizeof(double)));
+    h->cap_sens = n_dw + 2 * n_d;
+  }
+  int call_xbnd = 0;
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
+  double *d_dw = h->d_sens, *d_dl = h->d_sens + n_dw, *d_du = d_dl + n_d;
+  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_dl, dlbw, n_d * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_du, dubw, n_d * sizeof(double), hipMemcpyHostToDevice, s));
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_bnd(a, h->d_w, h->d_lam, h->d_lamx, d_dl, d_du, m, d_dw, h->d_status, s));
+  HIPCHK(hipMemcpyAsync(dw, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mpcx_sens_bounds_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                             const double* d_lam_x, const double* d_gw, int32_t m, double* d_glbw, double* d_gubw,
+                             int32_t* d_flag, void* stream) {
+  if (int r = check_sens_bounds_args(h, B, "sens_bounds_vjp", d_P && d_w && d_lam_g && d_lam_x && d_gw && d_glbw && d_gubw,
+                                     m))
+    return r;
+  if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_bnd_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_glbw, d_gubw, d_flag, (hipStream_t)stream));
+  return 0;
+}
+
+int mpcx_sens_bounds_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                         const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
+                         double* glbw, double* gubw, int32_t* flag) {
+  if (int r = check_sens_bounds_args(h, B, "sens_bounds_vjp", P && w && lam_g && lam_x && gw && glbw && gubw, m)) return r;
+  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  if (int r = ensure(h, B)) return r;
+  hipStream_t s = h->stream;
+  const size_t n_g = (size_t)B * m * h->nw;
+  if (3 * n_g > h->cap_sens) {
+    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
+    dev_free(h->d_sens);
+    h->cap_sens = 0;
+    HIPCHK(hipMalloc(&h->d_sens, 3 * n_g * sizeof(double)));
+    h->cap_sens = 3 * n_g;
+  }
+  int call_xbnd = 0;
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
+  double *d_gl = h->d_sens, *d_gu = d_gl + n_g, *d_gw = d_gu + n_g;
+  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_gw, gw, n_g * sizeof(double), hipMemcpyHostToDevice, s));
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_bnd_vjp(a, h->d_w, h->d_lam, h->d_lamx, d_gw, m, d_gl, d_gu, h->d_status, s));
+  HIPCHK(hipMemcpyAsync(glbw, d_gl, n_g * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(gubw, d_gu, n_g * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
 int mpcx_rk4_sens_dev(mpcx_handle* h, int32_t B, const double* d_X, const double* d_U, const double* d_xr,
                       double* d_J, void* stream) {
   if (!h || !d_X || !d_U || !d_xr || !d_J) return fail(MPCX_EINVAL, "null argument");

@@ -2432,6 +2432,34 @@ static hipError_t launch_sens_vjp_model(const SolveArgs& a, const double* W, con
   }
 }
 
+// sensitivities to the box bounds (sens.h sens_bnd_kernel, sens_bnd_vjp_kernel): the same lane groups;
+// m directions / cotangents per instance, 1 <= m <= NX.  Every model has them (no reference hook).
+template <class Model>
+static hipError_t launch_sens_bnd_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
+                                        const double* DLB, const double* DUB, int m, double* DW, int32_t* FLAG,
+                                        hipStream_t stream) {
+  if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
+  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+  const int blocks = (int)(((long)a.B * G + 63) / 64);
+  if (G == 16) hipLaunchKernelGGL((sens_bnd_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DLB, DUB, m, DW, FLAG);
+  else if (G == 32) hipLaunchKernelGGL((sens_bnd_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DLB, DUB, m, DW, FLAG);
+  else hipLaunchKernelGGL((sens_bnd_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DLB, DUB, m, DW, FLAG);
+  return hipGetLastError();
+}
+
+template <class Model>
+static hipError_t launch_sens_bnd_vjp_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
+                                            const double* GW, int m, double* GLB, double* GUB, int32_t* FLAG,
+                                            hipStream_t stream) {
+  if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
+  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+  const int blocks = (int)(((long)a.B * G + 63) / 64);
+  if (G == 16) hipLaunchKernelGGL((sens_bnd_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GLB, GUB, FLAG);
+  else if (G == 32) hipLaunchKernelGGL((sens_bnd_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GLB, GUB, FLAG);
+  else hipLaunchKernelGGL((sens_bnd_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GLB, GUB, FLAG);
+  return hipGetLastError();
+}
+
 #ifdef MPCX_STAMPS
 // diagnostic build: this unit's setters of its own copies of the stamp/counter pointers
 static int diag_set_stamps(void* d) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_stamps), &d, sizeof(void*)); }
@@ -2461,6 +2489,8 @@ static ModelOps model_ops_of(const char* name) {
                   launch_sens_model<Model>,
                   launch_sens_p_model<Model>,
                   launch_sens_vjp_model<Model>,
+                  launch_sens_bnd_model<Model>,
+                  launch_sens_bnd_vjp_model<Model>,
   };
 }
 

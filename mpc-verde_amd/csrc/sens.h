@@ -22,6 +22,8 @@
 // The second kernel of the file, sens_p_kernel (below), solves the same system for
 // directions of the whole parameter row: the references and targets beside x0; the third,
 // sens_vjp_kernel, the transpose: the gradient of a loss on w for the whole row.
+// sens_bnd_kernel and sens_bnd_vjp_kernel are the same pair for directions of the
+// box bounds lbw / ubw, for every model.
 // Included by kernels.h.
 #pragma once
 
@@ -924,6 +926,246 @@ __global__ __launch_bounds__(64) void sens_vjp_kernel(SolveArgs a, const double*
           if (i < slot.n) gp[slot.off + i] = regular ? gzr[i * NX + c] : nan;
       if (tails)
         for (int j = tail; j < np; ++j) gp[j] = regular ? 0.0 : nan;
+    }
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Sensitivities to the box bounds.  With the complementarity products
+// zL_i (w_i - lb_i) and zU_i (ub_i - w_i) held fixed, a direction (dlb, dub) of the bounds, each shaped
+// like w, enters the KKT system of sens_p_kernel through the right-hand side alone:
+//   r_i = -(sigL_i dlb_i + sigU_i dub_i),   sigL_i = zL_i / (w_i - lb_i),   sigU_i = zU_i / (ub_i - w_i),
+// on every bounded variable, the X rows of node N included (rq_N != 0); d_k = 0, dX_0 = 0.  No model
+// hook is involved, so every model has these kernels, the path-frame bicycle too.  zL = max(-lam_x, 0)
+// and zU = max(lam_x, 0) are sens_factor's one-sided split of the returned multiplier zU - zL: at most
+// one of sigL, sigU is non-zero per variable, and their sum is the Sigma of the factors.  On a
+// two-sided box the split is wrong by O(mu) (the far side's multiplier mu / slack is dropped), like
+// the rest of §3.5.  The transpose (sens_bnd_vjp_kernel): with z~ the adjoint solve of
+// sens_vjp_kernel (rq_k = gX_k, rr_k = gU_k, zero start),
+//   g_lb_i = -sigL_i z~_i,   g_ub_i = -sigU_i z~_i,   <g, dw> = <g_lb, dlb> + <g_ub, dub>.
+
+// sigL, sigU of my variables from the loads sens_factor makes (SensSys keeps only their sum); zero
+// where there is no finite bound, on X_0 and on the lanes beyond the horizon
+template <class Model>
+__device__ __forceinline__ void sens_bnd_sigma(const SolveArgs& a, const double* __restrict__ W,
+                                               const double* __restrict__ LX, int k, int inst, bool hasX, bool hasU,
+                                               double* sL, double* sU) {
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU;
+  const int nw = NX + NZ * a.N;
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) sL[i] = sU[i] = 0.0;
+  if (!hasX) return;
+  const double* w = W + (size_t)inst * nw;
+  const double* l = LX + (size_t)inst * nw;
+  const double* lbr = a.lbw + (size_t)inst * a.bnd_row;
+  const double* ubr = a.ubw + (size_t)inst * a.bnd_row;
+  auto one = [&](int i, int j) {
+    const double z = w[j], lx = l[j], lb = lbr[j], ub = ubr[j];
+    if (lb > -kInfBound) sL[i] = fmax(-lx, 0.0) / (z - lb);
+    if (ub < kInfBound) sU[i] = fmax(lx, 0.0) / (ub - z);
+  };
+  if (XBoundsOf<Model>::value && k > 0)
+    for (int i = 0; i < NX; ++i) one(i, ixw<NX, NU>(k, i));
+  if (hasU)
+    for (int i = 0; i < NU; ++i) one(NX + i, iuw<NX, NU>(k, i));
+}
+
+// W, LG, LX: the point, as for sens_kernel; DLB, DUB: B x m x nw directions of the lower and upper
+// bounds, each shaped like w (entries on X_0 and where the bound is not finite are not read);
+// DW: B x nw x m (sens_p_kernel's layout); FLAG: B or null (sens_kernel's).  1 <= m <= NX.
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_bnd_kernel(SolveArgs a, const double* __restrict__ W,
+                                                      const double* __restrict__ LG, const double* __restrict__ LX,
+                                                      const double* __restrict__ DLB, const double* __restrict__ DUB,
+                                                      int m, double* __restrict__ DW, int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+  double sL[NZ], sU[NZ];
+  sens_bnd_sigma<Model>(a, W, LX, k, inst, hasX, hasU, sL, sU);
+
+  // ---- right-hand sides, one column per direction: r = -(sigL dlb + sigU dub) on my bounded variables
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double r[NZ] = {};
+    if (c < m && hasX) {  // (c < m: launch-uniform)
+      const double* dl = DLB + ((size_t)inst * m + c) * nw;
+      const double* du = DUB + ((size_t)inst * m + c) * nw;
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) {  // (sigma is zero on the rows of U of node N)
+        const int j = (i < NX) ? ixw<NX, NU>(k, i) : iuw<NX, NU>(k, i - NX);
+        double e = 0.0;
+        if (sL[i] != 0.0) e = sL[i] * dl[j];
+        if (sU[i] != 0.0) e = fma(sU[i], du[j], e);
+        r[i] = -e;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      Rq[i * NX + c] = r[i];
+      Dd[i * NX + c] = 0.0;
+      X[i * NX + c] = 0.0;
+      pk[i * NX + c] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      Rr[l * NX + c] = r[NX + l];
+      U[l * NX + c] = 0.0;
+    }
+  }
+
+  // ---- the Riccati solve of the right-hand sides and one step of iterative refinement, as sens_p_kernel
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  // ---- regular: as sens_p_kernel
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  double* dw = DW + (size_t)(valid ? inst : 0) * nw * m;
+  if (hasX)
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)ixw<NX, NU>(k, i) * m + c] = regular ? X[i * NX + c] : nan;
+  if (hasU)
+    for (int l = 0; l < NU; ++l)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)iuw<NX, NU>(k, l) * m + c] = regular ? U[l * NX + c] : nan;
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
+}
+
+// W, LG, LX: the point, as for sens_kernel; GW: B x m x nw cotangents shaped like w; GLB, GUB: B x m x nw
+// gradient rows with respect to the lower and upper bounds, every entry written (0 on X_0 and where
+// the bound is not finite, NaN throughout for an irregular instance); FLAG: B or null.  1 <= m <= NX.
+// The regular test looks at the adjoint solution (X~, U~), which is all the outputs are formed from
+// (sens_vjp_kernel's also looks at the costates it contracts with).
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_bnd_vjp_kernel(SolveArgs a, const double* __restrict__ W,
+                                                          const double* __restrict__ LG, const double* __restrict__ LX,
+                                                          const double* __restrict__ GW, int m,
+                                                          double* __restrict__ GLB, double* __restrict__ GUB,
+                                                          int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+  double sL[NZ], sU[NZ];
+  sens_bnd_sigma<Model>(a, W, LX, k, inst, hasX, hasU, sL, sU);
+
+  // ---- right-hand sides, one column per cotangent, as sens_vjp_kernel
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double gx[NX] = {}, gu[NU] = {};
+    if (c < m) {  // (launch-uniform)
+      const double* gw = GW + ((size_t)(valid ? inst : 0) * m + c) * nw;
+      if (hasX)
+        for (int i = 0; i < NX; ++i) gx[i] = gw[ixw<NX, NU>(k, i)];
+      if (hasU)
+        for (int l = 0; l < NU; ++l) gu[l] = gw[iuw<NX, NU>(k, l)];
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      Rq[i * NX + c] = gx[i];
+      Dd[i * NX + c] = 0.0;
+      X[i * NX + c] = 0.0;
+      pk[i * NX + c] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      Rr[l * NX + c] = gu[l];
+      U[l * NX + c] = 0.0;
+    }
+  }
+
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  // ---- g_lb = -sigL z~, g_ub = -sigU z~: every lane writes its own variables' entries of every row
+  //      (a variable without a finite bound, and X_0: an exact 0)
+#pragma unroll
+  for (int c = 0; c < NX; ++c)
+    if (c < m && hasX) {
+      double* gl = GLB + ((size_t)inst * m + c) * nw;
+      double* gu = GUB + ((size_t)inst * m + c) * nw;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        const int j = ixw<NX, NU>(k, i);
+        gl[j] = regular ? -sL[i] * X[i * NX + c] : nan;
+        gu[j] = regular ? -sU[i] * X[i * NX + c] : nan;
+      }
+      if (hasU)
+#pragma unroll
+        for (int l = 0; l < NU; ++l) {
+          const int j = iuw<NX, NU>(k, l);
+          gl[j] = regular ? -sL[NX + l] * U[l * NX + c] : nan;
+          gu[j] = regular ? -sU[NX + l] * U[l * NX + c] : nan;
+        }
     }
   if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
 }

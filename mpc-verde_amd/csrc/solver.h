@@ -195,6 +195,14 @@ struct ModelOps {
   // like w, 1 <= m <= nx; GP (B x m x p_stride) gradient rows shaped like P, every entry written; FLAG as above
   hipError_t (*sens_vjp)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* GW,
                          int m, double* GP, int32_t* FLAG, hipStream_t stream);
+  // directional sensitivities to the box bounds at the same point (sens.h sens_bnd_kernel): DLB, DUB
+  // (B x m x nw) directions of lbw / ubw shaped like w, 1 <= m <= nx; DW (B x nw x m); FLAG as above
+  hipError_t (*sens_bnd)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* DLB,
+                         const double* DUB, int m, double* DW, int32_t* FLAG, hipStream_t stream);
+  // their transpose (sens.h sens_bnd_vjp_kernel): GW (B x m x nw) cotangents shaped like w; GLB, GUB
+  // (B x m x nw) gradient rows with respect to lbw / ubw, every entry written; FLAG as above
+  hipError_t (*sens_bnd_vjp)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* GW,
+                             int m, double* GLB, double* GUB, int32_t* FLAG, hipStream_t stream);
   // doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
   int ws_slots() const { return !resto ? 0 : RestoWs::slots(nx, nu) + (ws_stash ? chain_ws_slots(nx, nu) : 0); }
 };

@@ -40,7 +40,8 @@ EXPORTS = ("mpcx_default_spec", "mpcx_create", "mpcx_destroy", "mpcx_last_error"
            "mpcx_solve_batch_dev", "mpcx_plant_step", "mpcx_shift_dev", "mpcx_rk4_sens", "mpcx_rk4_sens_dev",
            "mpcx_set_linear_model", "mpcx_set_linear_tab_dev", "mpcx_step_dev", "mpcx_run_dev",
            "mpcx_source_hash", "mpcx_launch_shape", "mpcx_set_bounds_dev", "mpcx_sens_x0", "mpcx_sens_x0_dev",
-           "mpcx_sens_p", "mpcx_sens_p_dev", "mpcx_sens_vjp", "mpcx_sens_vjp_dev")
+           "mpcx_sens_p", "mpcx_sens_p_dev", "mpcx_sens_vjp", "mpcx_sens_vjp_dev", "mpcx_sens_bounds",
+           "mpcx_sens_bounds_dev", "mpcx_sens_bounds_vjp", "mpcx_sens_bounds_vjp_dev")
 STEP_COLD = 1
 STEP_PRIMAL_ONLY = 2
 
@@ -155,6 +156,10 @@ def load():
     lib.mpcx_sens_p_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]
     lib.mpcx_sens_vjp.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, dp, ip]
     lib.mpcx_sens_vjp_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]
+    lib.mpcx_sens_bounds.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, dp, ip]
+    lib.mpcx_sens_bounds_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]
+    lib.mpcx_sens_bounds_vjp.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, dp, dp, ip]
+    lib.mpcx_sens_bounds_vjp_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if an export is missing
     lib.mpcx_source_hash.restype = ctypes.c_char_p

@@ -22,7 +22,7 @@ import torch
 
 from .device import DeviceLoop
 
-__all__ = ["MPCFunction", "solve_differentiable"]
+__all__ = ["MPCFunction", "MPCBoundsFunction", "solve_differentiable"]
 
 
 class MPCFunction(torch.autograd.Function):
@@ -59,18 +59,94 @@ class MPCFunction(torch.autograd.Function):
         return gP, None, None
 
 
-def solve_differentiable(loop: DeviceLoop, P, irregular="nan"):
+class MPCBoundsFunction(torch.autograd.Function):
+    """forward(P, lbw, ubw, loop, zero_irregular): installs copies of the per-instance bounds
+    (``loop.set_bounds``), then as :class:`MPCFunction`.  backward: one ``loop.sens_bounds_vjp`` launch at
+    the saved point for ``lbw.grad`` / ``ubw.grad`` and, only when P requires a gradient, one
+    ``loop.sens_vjp`` launch for ``P.grad`` (so a model without ``sens_vjp``, the path-frame bicycle,
+    works with bounds gradients alone).  The backward differentiates at the forward's bounds: the
+    copies stay installed after the forward, and when the loop's installed bounds are no longer those
+    copies they are installed again for the launches and what was there is put back.
+
+    Host synchronisation: ``set_bounds`` validates the tensors on the loop's stream and waits for the
+    verdict, so the forward waits once for the stream, and the backward twice more only when it has to
+    re-install (once for the copies, once to put the others back).  The launches themselves never wait."""
+
+    @staticmethod
+    def forward(ctx, P, lbw, ubw, loop, zero_irregular):
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)
+        with torch.cuda.stream(loop.stream):
+            lb, ub = lbw.detach().clone(), ubw.detach().clone()
+        loop.set_bounds(lb, ub)
+        state = loop.solver._dev_bounds
+        with torch.cuda.stream(loop.stream):
+            loop.P.copy_(P.detach(), non_blocking=True)
+            loop.solve()
+            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
+            w = point[1].clone()
+        cur.wait_stream(loop.stream)
+        ctx.loop, ctx.zero_irregular, ctx.state = loop, zero_irregular, state
+        ctx.save_for_backward(*point, lb, ub)
+        return w
+
+    @staticmethod
+    def backward(ctx, gw):
+        loop = ctx.loop
+        *point, lb, ub = ctx.saved_tensors
+        before = loop.solver._dev_bounds
+        moved = before is not ctx.state
+        if moved:  # the forward's bounds, for the launches below
+            loop.set_bounds(lb, ub)
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)
+        gP = None
+        try:
+            with torch.cuda.stream(loop.stream):
+                g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
+                gl, gu, flag = loop.sens_bounds_vjp(g, point=point)
+                gl, gu = gl[:, 0], gu[:, 0]
+                if ctx.needs_input_grad[0]:
+                    gP, _ = loop.sens_vjp(g, point=point)  # (the same factors: the same flag)
+                    gP = gP[:, 0]
+                pd = getattr(loop.solver, "_pad", None)
+                if pd is not None:  # the bounds were given in the model's own layout
+                    idx = torch.from_numpy(pd.w_idx).to(loop.device)
+                    gl, gu = gl[:, idx], gu[:, idx]
+                if ctx.zero_irregular:
+                    bad = flag[:, None] != 0
+                    gl, gu = (torch.where(bad, torch.zeros_like(t), t) for t in (gl, gu))
+                    if gP is not None:
+                        gP = torch.where(bad, torch.zeros_like(gP), gP)
+        finally:
+            if moved:  # (stream-ordered after the launches; the validation waits for the stream)
+                loop.solver._install_bounds(before, loop.stream.cuda_stream if before is not None else None)
+        cur.wait_stream(loop.stream)
+        return gP, gl if ctx.needs_input_grad[1] else None, gu if ctx.needs_input_grad[2] else None, None, None
+
+
+def solve_differentiable(loop: DeviceLoop, P, irregular="nan", lbw=None, ubw=None):
     """Solve the loop's problems at P (B, n_p float64 device tensor, the loop's resident layout) and
     return w (B, n_w) with the backward described above.  The loop is used as it stands: its warm
     start is the one its next ``solve()`` would take, and its resident P, w, lam, lamx, status and
     iters are this solve's afterwards.
 
     irregular: what an instance flagged irregular (a variable on its bound, an indefinite reduced
-    Hessian) contributes to ``P.grad`` -- "nan" (default: its row is NaN, the others are unaffected)
-    or "zero" (its row is replaced by zeros)."""
+    Hessian) contributes to the gradients -- "nan" (default: its row is NaN, the others are unaffected)
+    or "zero" (its row is replaced by zeros).
+
+    lbw / ubw: None (the loop's bounds as they stand, :class:`MPCFunction`), or both (B, n_w) float64
+    device tensors in ``DeviceLoop.set_bounds``' layout: copies of them are installed as the loop's
+    per-instance bounds (and stay installed), and the backward fills ``lbw.grad`` / ``ubw.grad`` from one
+    ``sens_bounds_vjp`` launch; ``P.grad`` is computed only when P requires it
+    (:class:`MPCBoundsFunction`, which also says where the host waits)."""
     if irregular not in ("nan", "zero"):
         raise ValueError('irregular: "nan" or "zero"')
     if not isinstance(P, torch.Tensor) or P.dtype != torch.float64 or tuple(P.shape) != tuple(loop.P.shape) \
             or P.device != loop.device:
         raise ValueError(f"P: expected a float64 tensor of shape {tuple(loop.P.shape)} on {loop.device}")
-    return MPCFunction.apply(P, loop, irregular == "zero")
+    if lbw is None and ubw is None:
+        return MPCFunction.apply(P, loop, irregular == "zero")
+    if lbw is None or ubw is None:
+        raise ValueError("lbw and ubw must both be given (or both None)")
+    return MPCBoundsFunction.apply(P, lbw, ubw, loop, irregular == "zero")

@@ -181,6 +181,69 @@ class DeviceLoop:
                                                  ctypes_void(self.stream.cuda_stream)))
         return gP, flag
 
+    def _point(self, point):
+        n_p, nw, ng = self.P.shape[1], self.solver._h.n_w, self.lam.shape[1]
+        if point is None:
+            return self.P, self.w, self.lam, self.lamx
+        if len(point) != 4:
+            raise ValueError("point: expected (P, w, lam, lamx)")
+        for t, name, n in zip(point, ("point P", "point w", "point lam", "point lamx"), (n_p, nw, ng, nw)):
+            _check(t, name, torch.float64, (self.B, n), self.device)
+        return point
+
+    def sens_bounds(self, dlbw, dubw, dw_out=None, flag_out=None, point=None):
+        """Enqueue one bound-sensitivity launch (mpcx_sens_bounds_dev) at the loop's resident P, w, lam,
+        lamx and the bounds in force (``set_bounds``, else the problem's): dlbw / dubw (B, m, n_w)
+        float64 device tensors of m <= nx directions of the lower / upper bounds, each shaped like a
+        row of the resident w (the kernel's layout), either None (zeros), give dw (B, n_w, m) and
+        flag (B,) int32 (1 = irregular instance, NaN outputs).  point: as :meth:`sens_vjp`.  Tensors
+        given are written in place, the others are allocated; returns (dw, flag) without waiting for
+        the stream."""
+        nw, nx = self.solver._h.n_w, self._knx
+        given = dlbw if dlbw is not None else dubw
+        if not isinstance(given, torch.Tensor) or given.dim() != 3 or not 1 <= given.shape[1] <= nx:
+            raise ValueError(f"dlbw / dubw: expected ({self.B}, m, {nw}) tensors with 1 <= m <= {nx} (one may be None)")
+        m = given.shape[1]
+        with torch.cuda.stream(self.stream):
+            dlbw, dubw = (torch.zeros_like(given) if t is None else t for t in (dlbw, dubw))
+            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        _check(dlbw, "dlbw", torch.float64, (self.B, m, nw), self.device)
+        _check(dubw, "dubw", torch.float64, (self.B, m, nw), self.device)
+        point = self._point(point)
+        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_bounds_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
+                                                    _ptr(point[2]), _ptr(point[3]), _ptr(dlbw), _ptr(dubw), m, _ptr(dw),
+                                                    _ptr(flag), ctypes_void(self.stream.cuda_stream)))
+        return dw, flag
+
+    def sens_bounds_vjp(self, gw, glbw_out=None, gubw_out=None, flag_out=None, point=None):
+        """Enqueue one launch of the reverse mode of :meth:`sens_bounds` (mpcx_sens_bounds_vjp_dev): gw
+        (B, m, n_w) float64 device tensor of m <= nx cotangents shaped like rows of the resident w gives
+        glbw, gubw (B, m, n_w), the gradient rows with respect to the bounds in force (every entry
+        written: 0 where there is no finite bound), and flag (B,) int32.  point = (P, w, lam, lamx): as
+        :meth:`sens_vjp`; the bounds are always the ones in force at the call.  Returns (glbw, gubw,
+        flag) without waiting for the stream."""
+        nw, nx = self.solver._h.n_w, self._knx
+        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
+            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
+        m = gw.shape[1]
+        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
+        point = self._point(point)
+        with torch.cuda.stream(self.stream):
+            new = lambda: torch.empty((self.B, m, nw), dtype=torch.float64, device=self.device)  # noqa: E731
+            gl = new() if glbw_out is None else glbw_out
+            gu = new() if gubw_out is None else gubw_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        _check(gl, "glbw_out", torch.float64, (self.B, m, nw), self.device)
+        _check(gu, "gubw_out", torch.float64, (self.B, m, nw), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_bounds_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
+                                                        _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gl), _ptr(gu),
+                                                        _ptr(flag), ctypes_void(self.stream.cuda_stream)))
+        return gl, gu, flag
+
     def set_stage_refs(self, refs):
         """Per-step stage references (tracking, param layout x0_stageref): refs is a
         (B, N*(nx+nu)) float64 device tensor copied into P[:, nx:] on the loop's stream

@@ -406,6 +406,148 @@ class Solver:
         s = self.sens_vjp(P, res, gw, lbw, ubw)
         return {"dU0_dP": s["gP"], "flag": s["flag"]}
 
+    def _sens_bounds_point(self, P, res, lbw, ubw):
+        """What :meth:`sens_bounds` and :meth:`sens_bounds_vjp` share: the point and the bounds in the
+        kernel's layout.  Returns (B, P, w, lam, lamx, lbw, ubw, per_instance)."""
+        P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
+        B = P.shape[0]
+        if P.shape[1] != self.n_p:
+            raise ValueError(f"P: expected {self.n_p} columns, got {P.shape[1]}")
+        nw, ng = self._ms_nw, self._ms_ng
+        w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
+                        for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
+        lbw, ubw, per_instance = _batch_bounds(lbw, ubw, B, nw)
+        pd = self._pad
+        if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
+            P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
+            w, lamx = pd.scatter(w, pd.w_idx, pd.n_w_pad), pd.scatter(lamx, pd.w_idx, pd.n_w_pad)
+            lam = pd.scatter(lam, pd.g_idx, pd.n_g_pad)
+            if per_instance:
+                lbw, ubw = pd.scatter(lbw, pd.w_idx, pd.n_w_pad, -1e20), pd.scatter(ubw, pd.w_idx, pd.n_w_pad, 1e20)
+            else:
+                lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
+                ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
+        return B, P, w, lam, lamx, lbw, ubw, per_instance
+
+    def _with_bounds(self, B, lbw, ubw, per_instance, call):
+        """Run call(lbw, ubw) with (B, n_w) bounds installed as device bounds for its duration, as
+        ``solve_batch`` does (then whatever was installed before is put back); otherwise as given."""
+        if not per_instance:
+            return call(lbw, ubw)
+        import torch  # device memory comes from PyTorch, as in mpcx.device
+
+        dev = torch.device("cuda", self._h.spec.device)
+        before = self._dev_bounds
+        self._install_bounds((torch.from_numpy(lbw).to(dev), torch.from_numpy(ubw).to(dev), B, 1),
+                             torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            return call(None, None)
+        finally:  # (the host-pointer calls wait for their results)
+            self._install_bounds(before)
+
+    def sens_bounds(self, P, res, dlbw, dubw, lbw=None, ubw=None):
+        """Directional sensitivities of the solutions ``res`` to the box bounds (mpcx_sens_bounds):
+        dw = (d w*/d lbw) dlbw + (d w*/d ubw) dubw, no solve, every model.
+
+        dlbw / dubw: (B, m, n_w) directions of the lower / upper bounds, each shaped like a row of w, or
+        (B, n_w) for a single one; either may be None (zeros).  Any m (launches of at most nx columns
+        each; a column's bits do not depend on the others).  Entries on X_0 and where the bound is not
+        finite are ignored.
+        lbw / ubw: the bounds the solve used -- None (the problem's, or installed device bounds), a
+        scalar or n_w entries shared by the batch, or (B, n_w) arrays with one row per instance
+        (installed as device bounds for this call, as ``solve_batch`` does).
+        Returns {'dw': (B, n_w, m), 'flag': (B,)}: w(lbw + dlbw, ubw + dubw) ~ w + dw; a strictly active
+        variable moves with its bound, an inactive bound has an O(mu) effect.  flag 1 marks an
+        irregular instance (NaN outputs), as :meth:`sens_x0`.  These are barrier-problem sensitivities
+        with the one-sided multiplier split of include/mpcx.h (mpcx_sens_bounds)."""
+        if self.ocp.formulation == "single_shooting":
+            raise ValueError("sens_bounds: multiple-shooting layout only (bounds are given on its w)")
+        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
+        if dlbw is None and dubw is None:
+            raise ValueError("sens_bounds: at least one of dlbw / dubw must be given")
+        nwu = self._ms_nw
+        d = []
+        for v, name in ((dlbw, "dlbw"), (dubw, "dubw")):
+            if v is not None:
+                v = np.asarray(v, np.float64)
+                if v.ndim == 2:
+                    v = v[:, None, :]
+                if v.ndim != 3 or v.shape[0] != B or v.shape[2] != nwu or v.shape[1] < 1:
+                    raise ValueError(f"{name}: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {v.shape}")
+            d.append(v)
+        if d[0] is not None and d[1] is not None and d[0].shape != d[1].shape:
+            raise ValueError(f"dlbw {d[0].shape} and dubw {d[1].shape}: the same number of directions expected")
+        d = [np.zeros_like(d[1 - i]) if v is None else v for i, v in enumerate(d)]
+        m = d[0].shape[1]
+        nw, knx = nwu, self.ocp.nx
+        pd = self._pad
+        if pd is not None:
+            d = [pd.scatter(v.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1) for v in d]
+            nw, knx = pd.n_w_pad, pd.nxp
+        dw = np.empty((B, nw, m))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+
+        def call(lb, ub):
+            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
+                mc = min(knx, m - c0)
+                part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
+                dl, du = (np.ascontiguousarray(v[:, c0:c0 + mc]) for v in d)
+                _lib.check(lib.mpcx_sens_bounds(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
+                                                _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(dl),
+                                                _lib.dptr(du), mc, _lib.dptr(part), _lib.iptr(fl)))
+                dw[:, :, c0:c0 + mc] = part
+                np.bitwise_or(flag, fl, out=flag)
+
+        self._with_bounds(B, lbw, ubw, per_instance, call)
+        if pd is not None:  # the model's own states and inputs only
+            dw = dw[:, pd.w_idx]
+        return {"dw": np.ascontiguousarray(dw), "flag": flag}
+
+    def sens_bounds_vjp(self, P, res, gw, lbw=None, ubw=None):
+        """Reverse mode of :meth:`sens_bounds` (mpcx_sens_bounds_vjp): the gradients with respect to every
+        entry of lbw and ubw of a scalar loss whose gradient on the solution w is gw, from one launch:
+        <gw, sens_bounds(dlbw, dubw)> = <glbw, dlbw> + <gubw, dubw>.
+
+        gw: (B, m, n_w) cotangents or (B, n_w) for a single one; any m (launches of at most nx each).
+        lbw / ubw: as for :meth:`sens_bounds`.
+        Returns {'glbw': (B, m, n_w), 'gubw': (B, m, n_w), 'flag': (B,)}; the entries on X_0 and where
+        there is no finite bound are 0; flag 1 marks an irregular instance (NaN outputs)."""
+        if self.ocp.formulation == "single_shooting":
+            raise ValueError("sens_bounds_vjp: multiple-shooting layout only (bounds are given on its w)")
+        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
+        nwu = self._ms_nw
+        gw = np.asarray(gw, np.float64)
+        if gw.ndim == 2:
+            gw = gw[:, None, :]
+        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != nwu or gw.shape[1] < 1:
+            raise ValueError(f"gw: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {gw.shape}")
+        m = gw.shape[1]
+        nw, knx = nwu, self.ocp.nx
+        pd = self._pad
+        if pd is not None:
+            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
+            nw, knx = pd.n_w_pad, pd.nxp
+        gl, gu = np.empty((B, m, nw)), np.empty((B, m, nw))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+
+        def call(lb, ub):
+            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
+                mc = min(knx, m - c0)
+                pl, pu, fl = np.empty((B, mc, nw)), np.empty((B, mc, nw)), np.empty(B, np.int32)
+                gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
+                _lib.check(lib.mpcx_sens_bounds_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
+                                                    _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(gwc), mc,
+                                                    _lib.dptr(pl), _lib.dptr(pu), _lib.iptr(fl)))
+                gl[:, c0:c0 + mc], gu[:, c0:c0 + mc] = pl, pu
+                np.bitwise_or(flag, fl, out=flag)
+
+        self._with_bounds(B, lbw, ubw, per_instance, call)
+        if pd is not None:  # the model's own states and inputs only
+            gl, gu = gl[:, :, pd.w_idx], gu[:, :, pd.w_idx]
+        return {"glbw": np.ascontiguousarray(gl), "gubw": np.ascontiguousarray(gu), "flag": flag}
+
     def rk4_sens(self, w, P):
         """Per-interval defects, costs and Jacobians at w (B, n_w) -- the sweep kernel."""
         if self.ocp.model != "unicycle":

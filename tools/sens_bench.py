@@ -1,4 +1,5 @@
-"""Time of one sensitivity launch (mpcx_sens_x0_dev, mpcx_sens_p_dev, mpcx_sens_vjp_dev) next to one lock-step solve of the same batch.
+"""Time of one sensitivity launch (mpcx_sens_x0_dev, mpcx_sens_p_dev, mpcx_sens_vjp_dev, mpcx_sens_bounds_dev,
+mpcx_sens_bounds_vjp_dev) next to one lock-step solve of the same batch.
 
     python tools/sens_bench.py [B] [reps]      (defaults 1024, 9)
 
@@ -6,7 +7,9 @@ Two shapes: config 2 (unicycle point-to-point, N = 20) and the cart-pole QP at N
 is stepped twice (a cold and a warm closed-loop step), then every repetition times one warm
 lock-step step (DeviceLoop.step: solve + fused shift), one DeviceLoop.sens_x0 launch, one
 DeviceLoop.sens_p launch of m = 3 seeded directions over the whole parameter row and one
-DeviceLoop.sens_vjp launch of m = 3 and of m = 1 seeded cotangents over the whole of w at the loop's
+DeviceLoop.sens_vjp launch of m = 3 and of m = 1 seeded cotangents over the whole of w, and one
+DeviceLoop.sens_bounds launch of m = 3 seeded directions of both bounds and one
+DeviceLoop.sens_bounds_vjp launch of the m = 3 cotangents, all at the loop's
 resident solution, each with device events, after two warm-up repetitions.  Prints one JSON line per
 shape: medians, min-max spreads, and the ratios sens / solve, sens_p / sens_x0 and sens_vjp / sens_p."""
 import json
@@ -49,8 +52,13 @@ def main():
         gw1 = gw[:, :1].contiguous()
         gP, flagv = loop.sens_vjp(gw)
         gP1, _ = loop.sens_vjp(gw1)
+        dlb, dub = (torch.from_numpy(np.random.default_rng(s).normal(size=(B, m, loop.w.shape[1]))).to(loop.device)
+                    for s in (2, 3))
+        dwb, flagb = loop.sens_bounds(dlb, dub)
+        glb, gub, flagbv = loop.sens_bounds_vjp(gw)
         its = torch.zeros(B, dtype=torch.int32, device="cuda")
         solve_ms, sens_ms, sensp_ms, vjp_ms, vjp1_ms, it_max = [], [], [], [], [], []
+        bnd_ms, bvjp_ms = [], []
         for rep in range(reps + 2):
             a, b, c, d, e, f = ev(), ev(), ev(), ev(), ev(), ev()
             a.record()
@@ -69,6 +77,13 @@ def main():
             i.record()
             loop.sens_vjp(gw1, gP_out=gP1, flag_out=flagv)
             j.record()
+            k, l, o, p = ev(), ev(), ev(), ev()
+            k.record()
+            loop.sens_bounds(dlb, dub, dw_out=dwb, flag_out=flagb)
+            l.record()
+            o.record()
+            loop.sens_bounds_vjp(gw, glbw_out=glb, gubw_out=gub, flag_out=flagbv)
+            p.record()
             torch.cuda.synchronize()
             if rep >= 2:
                 solve_ms.append(a.elapsed_time(b))
@@ -76,9 +91,12 @@ def main():
                 sensp_ms.append(e.elapsed_time(f))
                 vjp_ms.append(g.elapsed_time(h))
                 vjp1_ms.append(i.elapsed_time(j))
+                bnd_ms.append(k.elapsed_time(l))
+                bvjp_ms.append(o.elapsed_time(p))
                 it_max.append(int(its.max()))
         solve_ms, sens_ms, sensp_ms = np.array(solve_ms), np.array(sens_ms), np.array(sensp_ms)
         vjp_ms, vjp1_ms = np.array(vjp_ms), np.array(vjp1_ms)
+        bnd_ms, bvjp_ms = np.array(bnd_ms), np.array(bvjp_ms)
         q = lambda v: {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4),  # noqa: E731
                        "max": round(float(v.max()), 4)}
         print(json.dumps({"shape": name, "N": ocp.N, "B": B, "reps": reps, "lockstep_step_ms": q(solve_ms),
@@ -88,6 +106,10 @@ def main():
                           "sens_vjp_m": m, "sens_vjp_ms": q(vjp_ms), "sens_vjp_m1_ms": q(vjp1_ms),
                           "ratio_sens_vjp_over_sens_p": round(float(np.median(vjp_ms) / np.median(sensp_ms)), 3),
                           "irregular_sens_vjp": int(flagv.sum()),
+                          "sens_bounds_m": m, "sens_bounds_ms": q(bnd_ms), "sens_bounds_vjp_ms": q(bvjp_ms),
+                          "ratio_sens_bounds_over_sens_p": round(float(np.median(bnd_ms) / np.median(sensp_ms)), 3),
+                          "ratio_sens_bounds_vjp_over_sens_vjp": round(float(np.median(bvjp_ms) / np.median(vjp_ms)), 3),
+                          "irregular_sens_bounds": int(flagb.sum()), "irregular_sens_bounds_vjp": int(flagbv.sum()),
                           "ipm_iterations_of_the_steps_max": it_max, "irregular": int(flag.sum()),
                           "irregular_sens_p": int(flagp.sum()),
                           "status_gt1": int((loop.status > 1).sum()), "source_hash": mpcx._lib.source_hash()}), flush=True)
