@@ -489,6 +489,74 @@ int mpcx_sens_bounds_vjp(mpcx_handle* h, int32_t B, const double* P, const doubl
                          const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
                          double* glbw, double* gubw, int32_t* flag);
 
+/* The cost weights as the sensitivity calls below see them: a stage's weight row has n_wt entries,
+ * nx + nu for the models with a diagonal cost (MPCX_MODEL_UNICYCLE and the ODE models), ordered
+ * (Q_0..Q_{nx-1}, R_0..R_{nu-1}), and nz (nz + 1) / 2 for MPCX_MODEL_LINEAR: the packed upper triangle of
+ * a stage table in mpcx_set_linear_model's layout of W, nz = nx + nu of the handle. */
+int mpcx_weight_dims(const mpcx_handle* h, int32_t* n_wt);
+
+/* Replace the diagonal weights Q (nx) and R (nu) of the handle's cost; host only, nothing is launched.
+ * Every later launch uses them, with results bit-identical to those of a handle created with these
+ * weights in its spec (a launch takes its weights from the spec each time; nothing else keeps them).
+ * MPCX_EINVAL, the handle unchanged: MPCX_MODEL_LINEAR (its weights are its tables:
+ * mpcx_set_linear_model), a NULL argument, an entry that is not finite or is negative. */
+int mpcx_set_weights(mpcx_handle* h, const double* Q, const double* R);
+
+/* Directional sensitivities of the solution to the cost weights at a primal-dual point as a solve
+ * returns it: dw = (dw* / dweights) dW for m directions of the weight rows.  One launch, no solve, every
+ * model; no reference counterpart -- it replaces central differences of whole solves on handles with
+ * perturbed weights.  Only the stage cost q_k depends on the weights, and linearly, so the KKT matrix is
+ * that of mpcx_sens_x0 (H_k + Sigma_k, A_k, B_k, stage 0 at (x0, U_0), P_N = Sigma_x) and a direction
+ * enters the right-hand side alone, per stage k < N,
+ *   r_k = d(grad_z q_k)/d(weights) . dW_k,    d_k = 0,  dX_0 = 0,  nothing on node N.
+ * Diagonal node costs (MPCX_COST_NODE, every ODE model): r_{k,i} = 2 dW_{k,i} e_{k,i} with e_k the
+ * residual of the model's own cost gradient -- z_k minus its reference; for MPCX_MODEL_PATH_BICYCLE
+ * (y - yt, phi - phit, v - vdes, s, d - d_ref, a - a_ref); its hook weight w_z = par[3] is no part of the
+ * row.  Unicycle with MPCX_COST_QUADRATURE: grad q is exactly linear and homogeneous in (Q, R), and r_k is
+ * the model's own gradient evaluated with the direction in the weights' place.  MPCX_MODEL_LINEAR:
+ * r_k = 2 dW_k (z_k - zr_k) with dW_k symmetric, packed as in mpcx_weight_dims.  The solve is
+ * mpcx_sens_p's (Riccati solve of right-hand sides, one step of iterative refinement).  These are
+ * barrier-problem sensitivities, as mpcx_sens_x0's.
+ *   dW     B x m x (per_stage ? N : 1) x n_wt, 1 <= m <= nx per call: one row per stage, or
+ *          (per_stage = 0) one row used at every stage; a row that is the same at every stage gives the
+ *          same bits either way.  Exact: a zero direction gives zeros.
+ *   dw     B x n_w x m, mpcx_sens_p's layout (the X_0 rows are exact zeros).  A column's bits do not
+ *          depend on the other columns or on m, nor an instance's on the batch it is in.
+ *   flag   as mpcx_sens_p.
+ * Bounds in force: as mpcx_sens_x0.  MPCX_EINVAL, with nothing launched: a NULL handle, B <= 0, a NULL
+ * pointer other than lbw / ubw / flag, m outside 1..nx, N >= 64.  The device variant only enqueues one
+ * launch on `stream`: it never synchronises, allocates nothing and can be captured in a graph. */
+int mpcx_sens_weights_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                          const double* d_lam_x, const double* d_dW, int32_t per_stage, int32_t m, double* d_dw,
+                          int32_t* d_flag, void* stream);
+int mpcx_sens_weights(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                      const double* lam_x, const double* lbw, const double* ubw, const double* dW, int32_t per_stage,
+                      int32_t m, double* dw, int32_t* flag);
+
+/* Reverse mode of mpcx_sens_weights: the gradients of a scalar loss on the solution with respect to every
+ * stage's weight row, and their sum over the stages, for m cotangents g shaped like w, from one launch; no
+ * reference counterpart (it replaces 2 n_wt finite-difference solves on new handles).  With z~ = (X~, U~)
+ * the adjoint solve of mpcx_sens_vjp (rq_k = gX_k on every node, rr_k = gU_k, zero start, one refinement
+ * step), <g, dw> = sum_{k<N} z~_k^T r_k, so per stage
+ *   diagonal costs:  gWk_{k,i} = 2 z~_{k,i} e_{k,i}
+ *   packed W:        gWk_k[a,a] = 2 z~_a e_a,   gWk_k[a,b] = 2 (z~_a e_b + z~_b e_a)  (a < b)
+ *   quadrature cost: gWk_{k,i} = z~_k^T grad q_k at the unit weight i
+ * and <g, dw> = <gWk, dW> for dw = mpcx_sens_weights(dW, per_stage = 1), to rounding.  X~_0 = 0, so stage
+ * 0's state weights get an exact zero from the node costs.  gW = sum_k gWk_k is the gradient for a
+ * direction applied to every stage alike: for the diagonal models, with respect to the handle's Q, R.
+ *   gw     B x m x n_w, 1 <= m <= nx per call
+ *   gWk    B x m x N x n_wt or NULL;  gW  B x m x n_wt or NULL; one of them is required.  Every entry of
+ *          those given is written, NaN throughout for an irregular instance.  A cotangent's bits do not
+ *          depend on the others or on m, nor an instance's on its batch; a zero cotangent gives zeros.
+ *   flag   as mpcx_sens_p.
+ * Bounds, refusals and the device variant: as mpcx_sens_weights. */
+int mpcx_sens_weights_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                              const double* d_lam_x, const double* d_gw, int32_t m, double* d_gWk, double* d_gW,
+                              int32_t* d_flag, void* stream);
+int mpcx_sens_weights_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                          const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
+                          double* gWk, double* gW, int32_t* flag);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2460,6 +2460,35 @@ static hipError_t launch_sens_bnd_vjp_model(const SolveArgs& a, const double* W,
   return hipGetLastError();
 }
 
+// sensitivities to the cost weights (sens.h sens_wt_kernel, sens_wt_vjp_kernel): the same lane groups;
+// m directions / cotangents per instance, 1 <= m <= NX; a weight row has Model::NWT entries
+template <class Model>
+static hipError_t launch_sens_wt_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
+                                       const double* DWT, int per_stage, int m, double* DW, int32_t* FLAG,
+                                       hipStream_t stream) {
+  if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
+  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+  const int blocks = (int)(((long)a.B * G + 63) / 64);
+  const int ps = per_stage ? 1 : 0;
+  if (G == 16) hipLaunchKernelGGL((sens_wt_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DWT, ps, m, DW, FLAG);
+  else if (G == 32) hipLaunchKernelGGL((sens_wt_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DWT, ps, m, DW, FLAG);
+  else hipLaunchKernelGGL((sens_wt_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DWT, ps, m, DW, FLAG);
+  return hipGetLastError();
+}
+
+template <class Model>
+static hipError_t launch_sens_wt_vjp_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
+                                           const double* GW, int m, double* GWK, double* GWS, int32_t* FLAG,
+                                           hipStream_t stream) {
+  if (a.N >= 64 || m < 1 || m > Model::NX || (!GWK && !GWS)) return hipErrorInvalidValue;
+  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+  const int blocks = (int)(((long)a.B * G + 63) / 64);
+  if (G == 16) hipLaunchKernelGGL((sens_wt_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GWK, GWS, FLAG);
+  else if (G == 32) hipLaunchKernelGGL((sens_wt_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GWK, GWS, FLAG);
+  else hipLaunchKernelGGL((sens_wt_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GWK, GWS, FLAG);
+  return hipGetLastError();
+}
+
 #ifdef MPCX_STAMPS
 // diagnostic build: this unit's setters of its own copies of the stamp/counter pointers
 static int diag_set_stamps(void* d) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_stamps), &d, sizeof(void*)); }
@@ -2491,6 +2520,9 @@ static ModelOps model_ops_of(const char* name) {
                   launch_sens_vjp_model<Model>,
                   launch_sens_bnd_model<Model>,
                   launch_sens_bnd_vjp_model<Model>,
+                  Model::NWT,
+                  launch_sens_wt_model<Model>,
+                  launch_sens_wt_vjp_model<Model>,
   };
 }
 

@@ -162,6 +162,59 @@ struct UnicycleModel {
       }
     }
   }
+  // The weight row of a stage: (Q_0..Q_2, R_0, R_1).
+  static constexpr int NWT = 5;
+  // Weight tangent of a stage (sens.h sens_wt_kernel; no solve kernel calls it): r = d(grad_z q)/d(Q, R) . dwt
+  // at fs = 1; F reads no weight, so d = 0 and the multipliers do not enter.  The node cost in closed form,
+  // 2 dwt_i e_i with e the residuals derivs forms.  The quadrature cost's gradient is exactly linear and
+  // homogeneous in (Q, R) -- its points do not depend on them -- so r is derivs' own gradient with the
+  // direction in the weights' place and zero multipliers: one call site, no second copy of the moment
+  // formulas, and a zero direction meets only products with 0.
+  __device__ __forceinline__ static void weight_tangent(const ModelArgs& a, const Ctx& c, const double* z,
+                                                        const double* dwt, double* r) {
+    if (a.sp.cost != 0) {
+      for (int i = 0; i < 3; ++i) r[i] = 2.0 * dwt[i] * (z[i] - c.xr[i]);
+      for (int i = 0; i < 2; ++i) r[3 + i] = 2.0 * dwt[3 + i] * (z[3 + i] - c.ur[i]);
+      return;
+    }
+    ModelArgs wa = a;
+    for (int i = 0; i < 3; ++i) wa.sp.Q[i] = dwt[i];
+    for (int i = 0; i < 2; ++i) wa.sp.R[i] = dwt[3 + i];
+    const double l0[3] = {};
+    double xf[3], q, A[9], Bm[6], H[15];
+    derivs(wa, c, z, l0, 1.0, xf, q, A, Bm, r, H);
+  }
+  // Weight cotangent of a stage (sens.h sens_wt_vjp_kernel; no solve kernel calls it), the transpose of
+  // weight_tangent for NX columns at once (xt: 3 x 3, ut: 2 x 3, gwt: 5 x 3, row = weight, column =
+  // cotangent; a column's bits do not depend on the others).  Node cost: 2 z~_i e_i.  Quadrature cost:
+  // row i is z~^T (derivs' gradient at the unit weight i), one call site run five times; a zero
+  // cotangent meets only products with 0.
+  __device__ __forceinline__ static void weight_cotangent(const ModelArgs& a, const Ctx& c, const double* z,
+                                                          const double* xt, const double* ut, double* gwt) {
+    if (a.sp.cost != 0) {
+      for (int cc = 0; cc < 3; ++cc) {
+        for (int i = 0; i < 3; ++i) gwt[i * 3 + cc] = 2.0 * xt[i * 3 + cc] * (z[i] - c.xr[i]);
+        for (int i = 0; i < 2; ++i) gwt[(3 + i) * 3 + cc] = 2.0 * ut[i * 3 + cc] * (z[3 + i] - c.ur[i]);
+      }
+      return;
+    }
+    for (int i = 0; i < 15; ++i) gwt[i] = 0.0;
+    const double l0[3] = {};
+#pragma unroll 1
+    for (int t = 0; t < 5; ++t) {  // the unit weight t
+      ModelArgs wa = a;
+      for (int i = 0; i < 3; ++i) wa.sp.Q[i] = (t == i) ? 1.0 : 0.0;
+      for (int i = 0; i < 2; ++i) wa.sp.R[i] = (t == i + 3) ? 1.0 : 0.0;
+      double xf[3], q, A[9], Bm[6], g[5], H[15];
+      derivs(wa, c, z, l0, 1.0, xf, q, A, Bm, g, H);
+      for (int cc = 0; cc < 3; ++cc) {
+        double e = g[0] * xt[cc];
+        for (int i = 1; i < 3; ++i) e = fma(g[i], xt[i * 3 + cc], e);
+        for (int i = 0; i < 2; ++i) e = fma(g[3 + i], ut[i * 3 + cc], e);
+        for (int j = 0; j < 5; ++j) gwt[j * 3 + cc] = (t == j) ? e : gwt[j * 3 + cc];
+      }
+    }
+  }
 };
 
 // The same model for problems without state bounds (configs 1 and 2: X free, |v| <= 1,
@@ -321,6 +374,41 @@ struct LinearModel {
         for (int j = 0; j < NU; ++j) wi = fma(c.W[symix(i, NX + j, NZ)], ut[j * NX + col], wi);
         gzr[i * NX + col] = -2.0 * wi;
       }
+  }
+  // The weight row of a stage: its table W_j, the packed upper triangle (mpcx_set_linear_model's layout).
+  static constexpr int NWT = NH;
+  // weight tangent (UnicycleModel::weight_tangent): r = 2 dW (z - zr_k), dW symmetric, the sum as derivs forms it
+  __device__ __forceinline__ static void weight_tangent(const ModelArgs&, const Ctx& c, const double* z,
+                                                        const double* dwt, double* r) {
+    double dz[NZ];
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) dz[i] = z[i] - c.zr[i];
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      double wi = 0.0;
+#pragma unroll
+      for (int j = 0; j < NZ; ++j) wi = fma(dwt[symix(i, j, NZ)], dz[j], wi);
+      r[i] = 2.0 * wi;
+    }
+  }
+  // weight cotangent (UnicycleModel::weight_cotangent): gW[a][a] = 2 z~_a e_a, gW[a][b] = 2 (z~_a e_b +
+  // z~_b e_a) for a < b (the packed entry stands for both W_ab and W_ba), NX columns (gwt: NH x NX)
+  __device__ __forceinline__ static void weight_cotangent(const ModelArgs&, const Ctx& c, const double* z,
+                                                          const double* xt, const double* ut, double* gwt) {
+    double dz[NZ];
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) dz[i] = z[i] - c.zr[i];
+#pragma unroll
+    for (int col = 0; col < NX; ++col) {
+      double zt[NZ];
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) zt[i] = i < NX ? xt[i * NX + col] : ut[(i - NX) * NX + col];
+#pragma unroll
+      for (int i = 0; i < NZ; ++i)
+#pragma unroll
+        for (int j = i; j < NZ; ++j)
+          gwt[symix(i, j, NZ) * NX + col] = (i == j) ? 2.0 * zt[i] * dz[i] : 2.0 * fma(zt[i], dz[j], zt[j] * dz[i]);
+    }
   }
 };
 

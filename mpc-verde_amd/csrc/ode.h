@@ -665,6 +665,29 @@ struct OdeModel {
 #pragma unroll
       for (int c = 0; c < NX; ++c) gzr[i * NX + c] = -2.0 * wgt(a, i) * (i < NX ? xt[i * NX + c] : ut[(i - NX) * NX + c]);
   }
+  // The weight row of a stage: (Q_0..Q_{NX-1}, R_0..R_{NU-1}), the diagonal of the node cost.  A cost hook's
+  // own weight (the path-frame bicycle's w_z) lives in par and is no part of it.
+  static constexpr int NWT = NZ;
+  // weight tangent (UnicycleModel::weight_tangent) of the diagonal node cost: r_i = 2 dwt_i e_i with the
+  // residual e_i = z_i - ref(c, i) of cost_derivs; every model, the ones with hooks too (F reads no weight)
+  __device__ __forceinline__ static void weight_tangent(const ModelArgs&, const Ctx& c, const double* z,
+                                                        const double* dwt, double* r) {
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      const double w2 = 2.0 * dwt[i];
+      r[i] = w2 * (z[i] - ref(c, i));
+    }
+  }
+  // weight cotangent (UnicycleModel::weight_cotangent): gwt_i = 2 z~_i e_i, NX columns (gwt: NZ x NX)
+  __device__ __forceinline__ static void weight_cotangent(const ModelArgs&, const Ctx& c, const double* z,
+                                                          const double* xt, const double* ut, double* gwt) {
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      const double e = z[i] - ref(c, i);
+#pragma unroll
+      for (int col = 0; col < NX; ++col) gwt[i * NX + col] = 2.0 * (i < NX ? xt[i * NX + col] : ut[(i - NX) * NX + col]) * e;
+    }
+  }
   // Exact derivatives by forward sensitivities and stage adjoints (Dyn::kAdjoint: closed-form
   // partials of f).  Everything in RK4 but f is linear, so with mu_e the adjoint of stage e's f
   // value in lam^T F and Tv_e = dv_e/dz the sensitivity of the variables f reads at stage e,

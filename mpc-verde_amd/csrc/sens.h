@@ -23,7 +23,8 @@
 // directions of the whole parameter row: the references and targets beside x0; the third,
 // sens_vjp_kernel, the transpose: the gradient of a loss on w for the whole row.
 // sens_bnd_kernel and sens_bnd_vjp_kernel are the same pair for directions of the
-// box bounds lbw / ubw, for every model.
+// box bounds lbw / ubw, for every model; sens_wt_kernel and sens_wt_vjp_kernel for
+// directions of the cost weights, through the models' weight_tangent / weight_cotangent hooks.
 // Included by kernels.h.
 #pragma once
 
@@ -1167,6 +1168,214 @@ __global__ __launch_bounds__(64) void sens_bnd_vjp_kernel(SolveArgs a, const dou
           gu[j] = regular ? -sU[NX + l] * U[l * NX + c] : nan;
         }
     }
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Sensitivities to the cost weights: Q, R of the diagonal costs, the stage tables W
+// of the linear model.  Only q_k depends on them, and linearly, so a direction of the weights leaves
+// the KKT matrix of sens_p_kernel as it is and enters the right-hand side alone:
+//   r_k = d(grad_z q_k)/d(weights) . dwt_k  (Model::weight_tangent),   d_k = 0,  dX_0 = 0,  rq_N = 0.
+// The transpose (sens_wt_vjp_kernel): with z~ = (X~, U~) the adjoint solve of sens_vjp_kernel,
+//   <g, dw> = sum_{k<N} z~_k^T r_k,   so stage k's own row gets  gwt_k = (dr_k/dwt_k)^T z~_k
+// (Model::weight_cotangent), and their sum over the stages is the gradient for a direction applied to
+// every stage alike: the handle's Q, R.  A weight row has Model::NWT entries.
+
+// W, LG, LX: the point, as for sens_kernel; DWT: B x m x (per_stage ? N : 1) x NWT directions of the
+// weight row, one per stage or one used at every stage (launch-uniform; a row that is the same at every
+// stage gives the same bits either way: only the address differs); DW: B x nw x m (sens_p_kernel's
+// layout, the X_0 rows exact zeros); FLAG: B or null (sens_kernel's).  1 <= m <= NX.
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_wt_kernel(SolveArgs a, const double* __restrict__ W,
+                                                     const double* __restrict__ LG, const double* __restrict__ LX,
+                                                     const double* __restrict__ DWT, int per_stage, int m,
+                                                     double* __restrict__ DW, int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX, NWT = Model::NWT;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+
+  // ---- right-hand sides, one column per direction: the stage's weight tangent at its evaluation point
+  const size_t rows = per_stage ? (size_t)N : 1, row = per_stage ? (size_t)k : 0;
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double r[NZ] = {};
+    if (c < m && hasU) {  // (c < m: launch-uniform; the hooks exchange nothing between lanes)
+      const double* dr = DWT + (((size_t)inst * m + c) * rows + row) * NWT;
+      double dwt[NWT];
+#pragma unroll
+      for (int i = 0; i < NWT; ++i) dwt[i] = dr[i];
+      Model::weight_tangent(ma, s.ctx, s.ze, dwt, r);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      Rq[i * NX + c] = hasU ? r[i] : 0.0;
+      Dd[i * NX + c] = 0.0;
+      X[i * NX + c] = 0.0;
+      pk[i * NX + c] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      Rr[l * NX + c] = hasU ? r[NX + l] : 0.0;
+      U[l * NX + c] = 0.0;
+    }
+  }
+
+  // ---- the Riccati solve of the right-hand sides and one step of iterative refinement, as sens_p_kernel
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  // ---- regular: as sens_p_kernel
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  double* dw = DW + (size_t)(valid ? inst : 0) * nw * m;
+  if (hasX)
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)ixw<NX, NU>(k, i) * m + c] = regular ? X[i * NX + c] : nan;
+  if (hasU)
+    for (int l = 0; l < NU; ++l)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)iuw<NX, NU>(k, l) * m + c] = regular ? U[l * NX + c] : nan;
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
+}
+
+// W, LG, LX: the point, as for sens_kernel; GW: B x m x nw cotangents shaped like w; GWK: B x m x N x NWT
+// gradient rows with respect to every stage's own weight row, or null; GWS: B x m x NWT, their sum over
+// the stages (gsum: the same bits whichever lane writes; lane 0 does), or null; every entry of the ones
+// given is written, NaN throughout for an irregular instance; FLAG: B or null.  1 <= m <= NX.  The
+// regular test is sens_bnd_vjp_kernel's: the adjoint solution is all the outputs are formed from.
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_wt_vjp_kernel(SolveArgs a, const double* __restrict__ W,
+                                                         const double* __restrict__ LG, const double* __restrict__ LX,
+                                                         const double* __restrict__ GW, int m,
+                                                         double* __restrict__ GWK, double* __restrict__ GWS,
+                                                         int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX, NWT = Model::NWT;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+
+  // ---- right-hand sides, one column per cotangent, as sens_vjp_kernel
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double gx[NX] = {}, gu[NU] = {};
+    if (c < m) {  // (launch-uniform)
+      const double* gw = GW + ((size_t)(valid ? inst : 0) * m + c) * nw;
+      if (hasX)
+        for (int i = 0; i < NX; ++i) gx[i] = gw[ixw<NX, NU>(k, i)];
+      if (hasU)
+        for (int l = 0; l < NU; ++l) gu[l] = gw[iuw<NX, NU>(k, l)];
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      Rq[i * NX + c] = gx[i];
+      Dd[i * NX + c] = 0.0;
+      X[i * NX + c] = 0.0;
+      pk[i * NX + c] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      Rr[l * NX + c] = gu[l];
+      U[l * NX + c] = 0.0;
+    }
+  }
+
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  // ---- contraction with the weight tangent: gwt_k = (dr_k/dwt_k)^T z~_k, all columns; zero beyond the
+  //      last stage (node N has no cost)
+  double gwt[NWT * NX];
+  Model::weight_cotangent(ma, s.ctx, s.ze, X, U, gwt);
+#pragma unroll
+  for (int i = 0; i < NWT * NX; ++i) gwt[i] = hasU ? gwt[i] : 0.0;
+  if (GWK && hasU)  // every stage lane writes its own rows
+#pragma unroll
+    for (int c = 0; c < NX; ++c)
+      if (c < m) {
+        double* gk = GWK + (((size_t)inst * m + c) * N + k) * NWT;
+#pragma unroll
+        for (int i = 0; i < NWT; ++i) gk[i] = regular ? gwt[i * NX + c] : nan;
+      }
+  if (GWS) {  // (launch-uniform) the stage sum: every lane ends with the same bits, lane 0 writes them
+#pragma unroll
+    for (int i = 0; i < NWT * NX; ++i) gwt[i] = gsum<G>(gwt[i], xw);
+    if (valid && k == 0)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) {
+          double* gs = GWS + ((size_t)inst * m + c) * NWT;
+#pragma unroll
+          for (int i = 0; i < NWT; ++i) gs[i] = regular ? gwt[i * NX + c] : nan;
+        }
+  }
   if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
 }
 

@@ -203,6 +203,16 @@ struct ModelOps {
   // (B x m x nw) gradient rows with respect to lbw / ubw, every entry written; FLAG as above
   hipError_t (*sens_bnd_vjp)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* GW,
                              int m, double* GLB, double* GUB, int32_t* FLAG, hipStream_t stream);
+  // entries of a stage's weight row (Model::NWT): nx + nu diagonal weights, or the packed table W
+  int n_wt;
+  // directional sensitivities to the cost weights at the same point (sens.h sens_wt_kernel): DWT
+  // (B x m x (per_stage ? N : 1) x n_wt) directions of the weight rows, 1 <= m <= nx; DW (B x nw x m); FLAG as above
+  hipError_t (*sens_wt)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* DWT,
+                        int per_stage, int m, double* DW, int32_t* FLAG, hipStream_t stream);
+  // their transpose (sens.h sens_wt_vjp_kernel): GW (B x m x nw) cotangents shaped like w; GWK (B x m x N x n_wt,
+  // per stage) and GWS (B x m x n_wt, the stage sum), either may be null but not both; FLAG as above
+  hipError_t (*sens_wt_vjp)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* GW,
+                            int m, double* GWK, double* GWS, int32_t* FLAG, hipStream_t stream);
   // doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
   int ws_slots() const { return !resto ? 0 : RestoWs::slots(nx, nu) + (ws_stash ? chain_ws_slots(nx, nu) : 0); }
 };

@@ -41,7 +41,9 @@ EXPORTS = ("mpcx_default_spec", "mpcx_create", "mpcx_destroy", "mpcx_last_error"
            "mpcx_set_linear_model", "mpcx_set_linear_tab_dev", "mpcx_step_dev", "mpcx_run_dev",
            "mpcx_source_hash", "mpcx_launch_shape", "mpcx_set_bounds_dev", "mpcx_sens_x0", "mpcx_sens_x0_dev",
            "mpcx_sens_p", "mpcx_sens_p_dev", "mpcx_sens_vjp", "mpcx_sens_vjp_dev", "mpcx_sens_bounds",
-           "mpcx_sens_bounds_dev", "mpcx_sens_bounds_vjp", "mpcx_sens_bounds_vjp_dev")
+           "mpcx_sens_bounds_dev", "mpcx_sens_bounds_vjp", "mpcx_sens_bounds_vjp_dev", "mpcx_weight_dims",
+           "mpcx_set_weights", "mpcx_sens_weights", "mpcx_sens_weights_dev", "mpcx_sens_weights_vjp",
+           "mpcx_sens_weights_vjp_dev")
 STEP_COLD = 1
 STEP_PRIMAL_ONLY = 2
 
@@ -160,6 +162,12 @@ def load():
     lib.mpcx_sens_bounds_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]
     lib.mpcx_sens_bounds_vjp.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, dp, dp, ip]
     lib.mpcx_sens_bounds_vjp_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]
+    lib.mpcx_weight_dims.argtypes = [H, ip]
+    lib.mpcx_set_weights.argtypes = [H, dp, dp]
+    lib.mpcx_sens_weights.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, ctypes.c_int32, dp, ip]
+    lib.mpcx_sens_weights_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]
+    lib.mpcx_sens_weights_vjp.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, dp, dp, ip]
+    lib.mpcx_sens_weights_vjp_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if an export is missing
     lib.mpcx_source_hash.restype = ctypes.c_char_p
@@ -235,6 +243,23 @@ class Handle:
         check(load().mpcx_set_bounds_dev(self._h, None if d_lbw is None else vp(d_lbw),
                                          None if d_ubw is None else vp(d_ubw), int(rows), int(n_steps),
                                          None if stream is None else vp(stream)))
+
+    def weight_dims(self):
+        """Entries of a stage's weight row (mpcx_weight_dims)."""
+        n = ctypes.c_int32()
+        check(load().mpcx_weight_dims(self._h, ctypes.byref(n)))
+        return n.value
+
+    def set_weights(self, Q, R):
+        """Replace the diagonal cost weights (mpcx_set_weights); the spec mirror follows."""
+        Q, R = (np.ascontiguousarray(v, np.float64).ravel() for v in (Q, R))
+        if Q.size != self._spec.nx or R.size != self._spec.nu:
+            raise ValueError(f"set_weights: expected Q ({self._spec.nx},) and R ({self._spec.nu},)")
+        check(load().mpcx_set_weights(self._h, dptr(Q), dptr(R)))
+        for i, v in enumerate(Q):
+            self._spec.Q[i] = v
+        for i, v in enumerate(R):
+            self._spec.R[i] = v
 
     @property
     def spec(self):

@@ -22,7 +22,7 @@ import torch
 
 from .device import DeviceLoop
 
-__all__ = ["MPCFunction", "MPCBoundsFunction", "solve_differentiable"]
+__all__ = ["MPCFunction", "MPCBoundsFunction", "MPCWeightsFunction", "solve_differentiable"]
 
 
 class MPCFunction(torch.autograd.Function):
@@ -125,7 +125,71 @@ class MPCBoundsFunction(torch.autograd.Function):
         return gP, gl if ctx.needs_input_grad[1] else None, gu if ctx.needs_input_grad[2] else None, None, None
 
 
-def solve_differentiable(loop: DeviceLoop, P, irregular="nan", lbw=None, ubw=None):
+class MPCWeightsFunction(torch.autograd.Function):
+    """forward(P, Q, R, loop, zero_irregular): sets the solver's diagonal cost weights from the values of
+    the tensors Q (nx,) and R (nu,), shared by the batch (``Solver.set_weights``; they stay set), then as
+    :class:`MPCFunction`.  backward: one ``loop.sens_weights_vjp`` launch at the saved point; ``Q.grad`` /
+    ``R.grad`` are its stage sums added over the batch (an instance flagged irregular puts NaN into the
+    sum unless irregular="zero" drops its row).  Only when P requires a gradient, one ``loop.sens_vjp``
+    launch for ``P.grad`` (so a model without ``sens_vjp``, the path-frame bicycle, works with weight
+    gradients alone).  The backward differentiates at the forward's weights: when the solver's weights
+    are no longer those, they are set for the launches and the others are put back.
+
+    Host synchronisation: the forward reads the values of Q and R on the host (one device-to-host copy,
+    which waits for the work that produces them), because the weights are launch arguments, not device
+    memory.  Nothing else waits; the backward's launches never do."""
+
+    @staticmethod
+    def forward(ctx, P, Q, R, loop, zero_irregular):
+        q, r = (tuple(float(v) for v in t.detach().cpu().tolist()) for t in (Q, R))  # (the one host read)
+        loop.solver.set_weights(q, r)
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)
+        with torch.cuda.stream(loop.stream):
+            loop.P.copy_(P.detach(), non_blocking=True)
+            loop.solve()
+            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
+            w = point[1].clone()
+        cur.wait_stream(loop.stream)
+        ctx.loop, ctx.zero_irregular, ctx.weights = loop, zero_irregular, (q, r)
+        ctx.save_for_backward(*point)
+        return w
+
+    @staticmethod
+    def backward(ctx, gw):
+        loop, solver = ctx.loop, ctx.loop.solver
+        point = ctx.saved_tensors
+        before = (tuple(solver.ocp.Q), tuple(solver.ocp.R))
+        moved = before != ctx.weights
+        if moved:  # the forward's weights, for the launches below (launch arguments: taken at the call)
+            solver.set_weights(*ctx.weights)
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)
+        gP = None
+        nx = solver.ocp.nx
+        try:
+            with torch.cuda.stream(loop.stream):
+                g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
+                _, gs, flag = loop.sens_weights_vjp(g, point=point, per_stage=False)
+                gs = gs[:, 0]
+                if ctx.needs_input_grad[0]:
+                    gP, _ = loop.sens_vjp(g, point=point)  # (the same factors: the same flag)
+                    gP = gP[:, 0]
+                if ctx.zero_irregular:
+                    bad = flag[:, None] != 0
+                    gs = torch.where(bad, torch.zeros_like(gs), gs)
+                    if gP is not None:
+                        gP = torch.where(bad, torch.zeros_like(gP), gP)
+                gs = gs.sum(dim=0)
+                gQ, gR = gs[:nx].contiguous(), gs[nx:].contiguous()
+        finally:
+            if moved:
+                solver.set_weights(*before)
+        cur.wait_stream(loop.stream)
+        return gP, gQ if ctx.needs_input_grad[1] else None, gR if ctx.needs_input_grad[2] else None, None, None
+
+
+def solve_differentiable(loop: DeviceLoop, P, irregular="nan", lbw=None, ubw=None, Q=None, R=None):
     """Solve the loop's problems at P (B, n_p float64 device tensor, the loop's resident layout) and
     return w (B, n_w) with the backward described above.  The loop is used as it stands: its warm
     start is the one its next ``solve()`` would take, and its resident P, w, lam, lamx, status and
@@ -139,12 +203,31 @@ def solve_differentiable(loop: DeviceLoop, P, irregular="nan", lbw=None, ubw=Non
     device tensors in ``DeviceLoop.set_bounds``' layout: copies of them are installed as the loop's
     per-instance bounds (and stay installed), and the backward fills ``lbw.grad`` / ``ubw.grad`` from one
     ``sens_bounds_vjp`` launch; ``P.grad`` is computed only when P requires it
-    (:class:`MPCBoundsFunction`, which also says where the host waits)."""
+    (:class:`MPCBoundsFunction`, which also says where the host waits).
+
+    Q / R: None, or both float64 device tensors of shape (nx,) and (nu,): the diagonal cost weights, shared
+    by the batch.  The solver's weights are set from their values (one host read of the two tensors; they
+    stay set), and the backward fills ``Q.grad`` / ``R.grad`` with the stage-and-batch sum from one
+    ``sens_weights_vjp`` launch; ``P.grad`` is computed only when P requires it
+    (:class:`MPCWeightsFunction`).  Not together with lbw / ubw, and not for linear models, whose weights
+    are their tables (``Solver.sens_weights_vjp`` gives their gradients)."""
     if irregular not in ("nan", "zero"):
         raise ValueError('irregular: "nan" or "zero"')
     if not isinstance(P, torch.Tensor) or P.dtype != torch.float64 or tuple(P.shape) != tuple(loop.P.shape) \
             or P.device != loop.device:
         raise ValueError(f"P: expected a float64 tensor of shape {tuple(loop.P.shape)} on {loop.device}")
+    if Q is not None or R is not None:
+        if lbw is not None or ubw is not None:
+            raise ValueError("Q / R and lbw / ubw cannot be combined")
+        if loop.solver.ocp.model == "linear":
+            raise ValueError("Q / R: a linear model's weights are its tables (Solver.sens_weights_vjp)")
+        if Q is None or R is None:
+            raise ValueError("Q and R must both be given (or both None)")
+        for t, name, n in ((Q, "Q", loop.solver.ocp.nx), (R, "R", loop.solver.ocp.nu)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (n,) \
+                    or t.device != loop.device:
+                raise ValueError(f"{name}: expected a float64 tensor of shape ({n},) on {loop.device}")
+        return MPCWeightsFunction.apply(P, Q, R, loop, irregular == "zero")
     if lbw is None and ubw is None:
         return MPCFunction.apply(P, loop, irregular == "zero")
     if lbw is None or ubw is None:

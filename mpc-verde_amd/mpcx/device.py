@@ -244,6 +244,59 @@ class DeviceLoop:
                                                         _ptr(flag), ctypes_void(self.stream.cuda_stream)))
         return gl, gu, flag
 
+    def sens_weights(self, dW, dw_out=None, flag_out=None, point=None):
+        """Enqueue one weight-sensitivity launch (mpcx_sens_weights_dev) at the loop's resident P, w, lam,
+        lamx, the solver's weights and the bounds in force: dW a float64 device tensor of m <= nx
+        directions of the weight rows in the kernel's layout (n_wt = ``solver._h.weight_dims()`` entries:
+        (Q, R), or a padded linear model's packed table, pad entries included), (B, m, n_wt) for rows
+        used at every stage or (B, m, N, n_wt) for one row per stage, gives dw (B, n_w, m) and flag (B,)
+        int32 (1 = irregular instance, NaN outputs).  point: as :meth:`sens_vjp`.  Tensors given are
+        written in place, the others are allocated; returns (dw, flag) without waiting for the stream."""
+        nw, nx, N, n_wt = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.weight_dims()
+        if not isinstance(dW, torch.Tensor) or dW.dim() not in (3, 4) or not 1 <= dW.shape[1] <= nx:
+            raise ValueError(f"dW: expected a ({self.B}, m, {n_wt}) or ({self.B}, m, {N}, {n_wt}) tensor with "
+                             f"1 <= m <= {nx}")
+        m, per_stage = dW.shape[1], int(dW.dim() == 4)
+        _check(dW, "dW", torch.float64, (self.B, m, N, n_wt) if per_stage else (self.B, m, n_wt), self.device)
+        point = self._point(point)
+        with torch.cuda.stream(self.stream):
+            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_weights_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
+                                                     _ptr(point[2]), _ptr(point[3]), _ptr(dW), per_stage, m, _ptr(dw),
+                                                     _ptr(flag), ctypes_void(self.stream.cuda_stream)))
+        return dw, flag
+
+    def sens_weights_vjp(self, gw, gWk_out=None, gW_out=None, flag_out=None, point=None, per_stage=True):
+        """Enqueue one launch of the reverse mode of :meth:`sens_weights` (mpcx_sens_weights_vjp_dev): gw
+        (B, m, n_w) float64 device tensor of m <= nx cotangents shaped like rows of the resident w gives
+        gWk (B, m, N, n_wt), the gradient rows with respect to every stage's own weight row (None with
+        per_stage=False and no gWk_out: not computed), gW (B, m, n_wt), their sum over the stages, and
+        flag (B,) int32, in the kernel's layout.  point = (P, w, lam, lamx): as :meth:`sens_vjp`; the
+        weights and bounds are the ones in force at the call.  Returns (gWk, gW, flag) without waiting
+        for the stream."""
+        nw, nx, N, n_wt = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.weight_dims()
+        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
+            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
+        m = gw.shape[1]
+        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
+        point = self._point(point)
+        with torch.cuda.stream(self.stream):
+            new = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)  # noqa: E731
+            gk = gWk_out if gWk_out is not None else (new(self.B, m, N, n_wt) if per_stage else None)
+            gs = new(self.B, m, n_wt) if gW_out is None else gW_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        if gk is not None:
+            _check(gk, "gWk_out", torch.float64, (self.B, m, N, n_wt), self.device)
+        _check(gs, "gW_out", torch.float64, (self.B, m, n_wt), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_weights_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
+                                                         _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gk),
+                                                         _ptr(gs), _ptr(flag), ctypes_void(self.stream.cuda_stream)))
+        return gk, gs, flag
+
     def set_stage_refs(self, refs):
         """Per-step stage references (tracking, param layout x0_stageref): refs is a
         (B, N*(nx+nu)) float64 device tensor copied into P[:, nx:] on the loop's stream

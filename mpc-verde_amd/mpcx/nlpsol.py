@@ -21,6 +21,7 @@ Here:
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import time
 
@@ -547,6 +548,162 @@ class Solver:
         if pd is not None:  # the model's own states and inputs only
             gl, gu = gl[:, :, pd.w_idx], gu[:, :, pd.w_idx]
         return {"glbw": np.ascontiguousarray(gl), "gubw": np.ascontiguousarray(gu), "flag": flag}
+
+    def set_weights(self, Q, R):
+        """Replace the diagonal cost weights Q (nx) and R (nu) of the problem (mpcx_set_weights; not for
+        linear models, whose weights are their tables): every later solve and sensitivity call uses them,
+        bit for bit as a solver created with these weights would."""
+        if self.ocp.model == "linear":
+            raise ValueError("set_weights: a linear model's weights are its tables (set_linear_model)")
+        self._h.set_weights(Q, R)
+        self.ocp = dataclasses.replace(self.ocp, Q=tuple(float(v) for v in np.ravel(Q)),
+                                       R=tuple(float(v) for v in np.ravel(R)))
+
+    def _wt_sel(self):
+        """Where the entries of the problem's own packed W lie in the kernel's packed weight row."""
+        nz = self.ocp.nx + self.ocp.nu
+        pd = self._pad
+        nzk = nz if pd is None else pd.nxp + self.ocp.nu
+        ix = np.arange(nz) if pd is None else np.r_[np.arange(self.ocp.nx), pd.nxp + np.arange(self.ocp.nu)]
+        iu = np.triu_indices(nz)
+        a, b = ix[iu[0]], ix[iu[1]]
+        return a * nzk - a * (a - 1) // 2 + (b - a), nzk * (nzk + 1) // 2
+
+    def _weight_rows(self, B, dQ, dR, dW):
+        """The directions of :meth:`sens_weights` as (B, m, N or 1, n_wt) in the kernel's layout."""
+        lin = self.ocp.model == "linear"
+        if lin != (dW is not None) or (lin and (dQ is not None or dR is not None)):
+            raise ValueError("sens_weights: dW for a linear model, dQ / dR for the others")
+        N = self.ocp.N
+
+        def rows(v, n, name):
+            v = np.asarray(v, np.float64)
+            if v.ndim == 2:
+                v = v[:, None, None, :]
+            elif v.ndim == 3:
+                v = v[:, :, None, :]
+            if v.ndim != 4 or v.shape[0] != B or v.shape[1] < 1 or v.shape[2] not in (1, N) or v.shape[3] != n:
+                raise ValueError(f"{name}: expected ({B}, {n}), ({B}, m, {n}) or ({B}, m, {N}, {n}), got {v.shape}")
+            return v
+
+        if lin:
+            sel, n_k = self._wt_sel()
+            v = rows(dW, sel.size, "dW")
+            d = np.zeros(v.shape[:3] + (n_k,))
+            d[..., sel] = v
+            return d
+        if dQ is None and dR is None:
+            raise ValueError("sens_weights: at least one of dQ / dR must be given")
+        q = None if dQ is None else rows(dQ, self.ocp.nx, "dQ")
+        r = None if dR is None else rows(dR, self.ocp.nu, "dR")
+        q = np.zeros(r.shape[:3] + (self.ocp.nx,)) if q is None else q
+        r = np.zeros(q.shape[:3] + (self.ocp.nu,)) if r is None else r
+        if q.shape[:2] != r.shape[:2]:
+            raise ValueError(f"dQ {q.shape} and dR {r.shape}: the same number of directions expected")
+        if q.shape[2] != r.shape[2]:  # one of them per stage: the other repeated
+            q, r = (np.broadcast_to(v, v.shape[:2] + (N,) + v.shape[3:]) for v in (q, r))
+        return np.concatenate([q, r], axis=3)
+
+    def sens_weights(self, P, res, dQ=None, dR=None, dW=None, lbw=None, ubw=None):
+        """Directional sensitivities of the solutions ``res`` to the cost weights (mpcx_sens_weights):
+        dw = (d w*/d weights) d(weights), no solve, every model.
+
+        dQ / dR (the unicycle and the ODE models): directions of the diagonal weights, (B, nx) / (B, nu)
+        for a single one, (B, m, nx) / (B, m, nu) for m of them used at every stage, or per stage
+        (B, m, N, nx) / (B, m, N, nu); either may be None (zeros).
+        dW (linear models): the same shapes with the packed upper triangle (``lti.pack_sym``) of a
+        symmetric direction of the stage table in the problem's own (x, u) in place of the rows.
+        Any m (launches of at most nx columns each; a column's bits do not depend on the others).
+        lbw / ubw: as for :meth:`sens_bounds`.
+        Returns {'dw': (B, n_w, m), 'flag': (B,)}: w(weights + d) ~ w + dw (the X_0 rows are exact
+        zeros); flag 1 marks an irregular instance (NaN outputs), as :meth:`sens_x0`.  Barrier-problem
+        sensitivities (include/mpcx.h, mpcx_sens_weights)."""
+        if self.ocp.formulation == "single_shooting":
+            raise ValueError("sens_weights: multiple-shooting layout only")
+        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
+        d = self._weight_rows(B, dQ, dR, dW)
+        m, per_stage = d.shape[1], int(d.shape[2] > 1)
+        nw, knx = self._ms_nw, self.ocp.nx
+        pd = self._pad
+        if pd is not None:
+            nw, knx = pd.n_w_pad, pd.nxp
+        dw = np.empty((B, nw, m))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+
+        def call(lb, ub):
+            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
+                mc = min(knx, m - c0)
+                part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
+                dc = np.ascontiguousarray(d[:, c0:c0 + mc])
+                _lib.check(lib.mpcx_sens_weights(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
+                                                 _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(dc),
+                                                 per_stage, mc, _lib.dptr(part), _lib.iptr(fl)))
+                dw[:, :, c0:c0 + mc] = part
+                np.bitwise_or(flag, fl, out=flag)
+
+        self._with_bounds(B, lbw, ubw, per_instance, call)
+        if pd is not None:  # the model's own states and inputs only
+            dw = dw[:, pd.w_idx]
+        return {"dw": np.ascontiguousarray(dw), "flag": flag}
+
+    def sens_weights_vjp(self, P, res, gw, lbw=None, ubw=None):
+        """Reverse mode of :meth:`sens_weights` (mpcx_sens_weights_vjp): the gradients with respect to the
+        cost weights of a scalar loss whose gradient on the solution w is gw, from one launch:
+        <gw, sens_weights(per-stage d)> = <gQk, dQ> + <gRk, dR>  (linear models: <gWk, dW>).
+
+        gw: (B, m, n_w) cotangents or (B, n_w) for a single one; any m (launches of at most nx each).
+        lbw / ubw: as for :meth:`sens_bounds`.
+        Returns 'flag' (B,) and, for the unicycle and the ODE models, 'gQk' (B, m, N, nx), 'gRk'
+        (B, m, N, nu) per stage and their sums over the stages 'gQ' (B, m, nx), 'gR' (B, m, nu): the
+        gradient with respect to the problem's Q, R.  For linear models 'gWk' (B, m, N, nz (nz + 1) / 2),
+        packed as dW of :meth:`sens_weights`, and 'gW' (B, m, n_tab, .): the stages' rows summed per
+        table through the instance's schedule.  NaN outputs where flag is 1."""
+        if self.ocp.formulation == "single_shooting":
+            raise ValueError("sens_weights_vjp: multiple-shooting layout only")
+        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
+        nwu = self._ms_nw
+        gw = np.asarray(gw, np.float64)
+        if gw.ndim == 2:
+            gw = gw[:, None, :]
+        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != nwu or gw.shape[1] < 1:
+            raise ValueError(f"gw: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {gw.shape}")
+        m, N = gw.shape[1], self.ocp.N
+        knx = self.ocp.nx
+        pd = self._pad
+        if pd is not None:
+            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
+            knx = pd.nxp
+        n_wt = self._h.weight_dims()
+        gk, gs = np.empty((B, m, N, n_wt)), np.empty((B, m, n_wt))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+
+        def call(lb, ub):
+            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
+                mc = min(knx, m - c0)
+                pk, ps, fl = np.empty((B, mc, N, n_wt)), np.empty((B, mc, n_wt)), np.empty(B, np.int32)
+                gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
+                _lib.check(lib.mpcx_sens_weights_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
+                                                     _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(gwc), mc,
+                                                     _lib.dptr(pk), _lib.dptr(ps), _lib.iptr(fl)))
+                gk[:, c0:c0 + mc], gs[:, c0:c0 + mc] = pk, ps
+                np.bitwise_or(flag, fl, out=flag)
+
+        self._with_bounds(B, lbw, ubw, per_instance, call)
+        if self.ocp.model != "linear":
+            nx = self.ocp.nx
+            return {"gQ": np.ascontiguousarray(gs[..., :nx]), "gR": np.ascontiguousarray(gs[..., nx:]),
+                    "gQk": np.ascontiguousarray(gk[..., :nx]), "gRk": np.ascontiguousarray(gk[..., nx:]), "flag": flag}
+        sel, _ = self._wt_sel()
+        gk = np.ascontiguousarray(gk[..., sel])
+        tab = np.asarray(self.ocp.tab)
+        tab = tab[None, :] if tab.ndim == 1 else tab
+        tab = np.broadcast_to(tab, (B, N)) if tab.shape[0] == 1 else tab[:B]
+        gW = np.zeros((B, m, self.ocp.n_tab, sel.size))
+        bi = np.broadcast_to(np.arange(B)[:, None], (B, N))
+        np.add.at(gW, (bi[:, None, :], np.arange(m)[None, :, None], tab[:, None, :]), gk)
+        return {"gWk": gk, "gW": gW, "flag": flag}
 
     def rk4_sens(self, w, P):
         """Per-interval defects, costs and Jacobians at w (B, n_w) -- the sweep kernel."""

@@ -1,5 +1,6 @@
 """Time of one sensitivity launch (mpcx_sens_x0_dev, mpcx_sens_p_dev, mpcx_sens_vjp_dev, mpcx_sens_bounds_dev,
-mpcx_sens_bounds_vjp_dev) next to one lock-step solve of the same batch.
+mpcx_sens_bounds_vjp_dev, mpcx_sens_weights_dev, mpcx_sens_weights_vjp_dev) next to one lock-step solve of the
+same batch.
 
     python tools/sens_bench.py [B] [reps]      (defaults 1024, 9)
 
@@ -9,7 +10,9 @@ lock-step step (DeviceLoop.step: solve + fused shift), one DeviceLoop.sens_x0 la
 DeviceLoop.sens_p launch of m = 3 seeded directions over the whole parameter row and one
 DeviceLoop.sens_vjp launch of m = 3 and of m = 1 seeded cotangents over the whole of w, and one
 DeviceLoop.sens_bounds launch of m = 3 seeded directions of both bounds and one
-DeviceLoop.sens_bounds_vjp launch of the m = 3 cotangents, all at the loop's
+DeviceLoop.sens_bounds_vjp launch of the m = 3 cotangents, one DeviceLoop.sens_weights launch of m = 3
+seeded per-stage directions of the weight rows and one DeviceLoop.sens_weights_vjp launch of the m = 3
+cotangents (per-stage rows and their sum), all at the loop's
 resident solution, each with device events, after two warm-up repetitions.  Prints one JSON line per
 shape: medians, min-max spreads, and the ratios sens / solve, sens_p / sens_x0 and sens_vjp / sens_p."""
 import json
@@ -56,9 +59,13 @@ def main():
                     for s in (2, 3))
         dwb, flagb = loop.sens_bounds(dlb, dub)
         glb, gub, flagbv = loop.sens_bounds_vjp(gw)
+        n_wt = solver._h.weight_dims()
+        dwt = torch.from_numpy(np.random.default_rng(4).normal(size=(B, m, ocp.N, n_wt))).to(loop.device)
+        dww, flagw = loop.sens_weights(dwt)
+        gwk, gws, flagwv = loop.sens_weights_vjp(gw)
         its = torch.zeros(B, dtype=torch.int32, device="cuda")
         solve_ms, sens_ms, sensp_ms, vjp_ms, vjp1_ms, it_max = [], [], [], [], [], []
-        bnd_ms, bvjp_ms = [], []
+        bnd_ms, bvjp_ms, wt_ms, wvjp_ms = [], [], [], []
         for rep in range(reps + 2):
             a, b, c, d, e, f = ev(), ev(), ev(), ev(), ev(), ev()
             a.record()
@@ -84,6 +91,13 @@ def main():
             o.record()
             loop.sens_bounds_vjp(gw, glbw_out=glb, gubw_out=gub, flag_out=flagbv)
             p.record()
+            t, u, v, x = ev(), ev(), ev(), ev()
+            t.record()
+            loop.sens_weights(dwt, dw_out=dww, flag_out=flagw)
+            u.record()
+            v.record()
+            loop.sens_weights_vjp(gw, gWk_out=gwk, gW_out=gws, flag_out=flagwv)
+            x.record()
             torch.cuda.synchronize()
             if rep >= 2:
                 solve_ms.append(a.elapsed_time(b))
@@ -93,10 +107,13 @@ def main():
                 vjp1_ms.append(i.elapsed_time(j))
                 bnd_ms.append(k.elapsed_time(l))
                 bvjp_ms.append(o.elapsed_time(p))
+                wt_ms.append(t.elapsed_time(u))
+                wvjp_ms.append(v.elapsed_time(x))
                 it_max.append(int(its.max()))
         solve_ms, sens_ms, sensp_ms = np.array(solve_ms), np.array(sens_ms), np.array(sensp_ms)
         vjp_ms, vjp1_ms = np.array(vjp_ms), np.array(vjp1_ms)
         bnd_ms, bvjp_ms = np.array(bnd_ms), np.array(bvjp_ms)
+        wt_ms, wvjp_ms = np.array(wt_ms), np.array(wvjp_ms)
         q = lambda v: {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4),  # noqa: E731
                        "max": round(float(v.max()), 4)}
         print(json.dumps({"shape": name, "N": ocp.N, "B": B, "reps": reps, "lockstep_step_ms": q(solve_ms),
@@ -110,6 +127,10 @@ def main():
                           "ratio_sens_bounds_over_sens_p": round(float(np.median(bnd_ms) / np.median(sensp_ms)), 3),
                           "ratio_sens_bounds_vjp_over_sens_vjp": round(float(np.median(bvjp_ms) / np.median(vjp_ms)), 3),
                           "irregular_sens_bounds": int(flagb.sum()), "irregular_sens_bounds_vjp": int(flagbv.sum()),
+                          "sens_weights_m": m, "sens_weights_ms": q(wt_ms), "sens_weights_vjp_ms": q(wvjp_ms),
+                          "ratio_sens_weights_over_sens_bounds": round(float(np.median(wt_ms) / np.median(bnd_ms)), 3),
+                          "ratio_sens_weights_vjp_over_sens_bounds_vjp": round(float(np.median(wvjp_ms) / np.median(bvjp_ms)), 3),
+                          "irregular_sens_weights": int(flagw.sum()), "irregular_sens_weights_vjp": int(flagwv.sum()),
                           "ipm_iterations_of_the_steps_max": it_max, "irregular": int(flag.sum()),
                           "irregular_sens_p": int(flagp.sum()),
                           "status_gt1": int((loop.status > 1).sum()), "source_hash": mpcx._lib.source_hash()}), flush=True)
