@@ -1,9 +1,11 @@
 """Exact stage derivatives of the nonlinear ODE models in extended precision -- TEST INFRASTRUCTURE
-ONLY (tests/test_stage_derivs_cpu.py, tests/test_gpu_stage_derivs.py).
+ONLY (tests/test_stage_derivs_cpu.py, tests/test_gpu_stage_derivs.py; through helpers/sens_nonlinear_ref.py
+tests/test_sens_nonlinear_cpu.py and tests/test_gpu_sens_nonlinear.py).
 
 For the kinematic bicycle, the 6-state dynamic bicycle, the cart-pole and the path-frame bicycle
 this module restates, from the equations in ``mpcx/ode.py``'s docstring and ``oracle/ode_ref.py``
-(not from the kernel), the interval map F (RK4, M substeps of h = T/M) and the stage cost q, and
+(not from the kernel), the interval map F (RK4, M substeps of h = T/M) and the stage cost q -- and for
+the unicycle, from ``oracle/nlp_ref.py``, F with either of its costs (RK4 quadrature, node) -- and
 differentiates them with hyper-dual numbers v + a e1 + b e2 + ab e1 e2 (e1^2 = e2^2 = 0) over NumPy
 arrays: one pass seeded with (e_m, e_n) gives columns m and n of the first derivatives and the
 mixed second derivative, exactly (no truncation).  The scalar type is a parameter: ``np.longdouble``
@@ -24,7 +26,7 @@ import math
 import numpy as np
 
 MODEL_ID = {"kin_bicycle": 3, "dyn_bicycle": 4, "cartpole": 5, "path_bicycle": 6}  # tests/hip/derivs_check.hip
-NXU = {"kin_bicycle": (3, 2), "dyn_bicycle": (6, 2), "cartpole": (4, 1), "path_bicycle": (4, 2)}
+NXU = {"kin_bicycle": (3, 2), "dyn_bicycle": (6, 2), "cartpole": (4, 1), "path_bicycle": (4, 2), "unicycle": (3, 2)}
 # states f never reads (from the equations): their columns of dF/dx are unit vectors
 INDEP = {"kin_bicycle": (0, 1), "dyn_bicycle": (0, 1), "cartpole": (0,), "path_bicycle": ()}
 BLOCKS = ("xf", "q", "A", "B", "g", "H")
@@ -116,7 +118,7 @@ def _elementary(name):
 sin, cos, tan = _elementary("sin"), _elementary("cos"), _elementary("tan")
 
 
-# ---------------------------------------------------------------------------- the four models
+# ---------------------------------------------------------------------------- the four ODE models, the unicycle
 # x, u, par, row: sequences of scalars of one arithmetic (HD, ndarray, mpmath); returns the list dx
 def f_kin_bicycle(x, u, par, row):
     """x = (X, Y, psi), u = (v, delta): psi' = v tan(delta) / L."""
@@ -160,8 +162,14 @@ def f_path_bicycle(x, u, par, row):
     return [v * sin(e), v * (c2 * tan(c1 * delta) - kap * cos(e) / (1 - (y - yt) * kap)), a]
 
 
+def f_unicycle(x, u, par, row):
+    """x = (x, y, theta), u = (v, omega): oracle/nlp_ref.py ``rhs``."""
+    th, v, om = x[2], u[0], u[1]
+    return [v * cos(th), v * sin(th), om]
+
+
 F_OF = {"kin_bicycle": f_kin_bicycle, "dyn_bicycle": f_dyn_bicycle, "cartpole": f_cartpole,
-        "path_bicycle": f_path_bicycle}
+        "path_bicycle": f_path_bicycle, "unicycle": f_unicycle}
 
 
 def rk4(f, x, u, par, row, h, M):
@@ -198,11 +206,45 @@ def stage_cost(model, z, row, W, par):
     return q
 
 
+def unicycle_stage(z, row, W, T, M, cost):
+    """(x+, q) of the unicycle, restated from oracle/nlp_ref.py ``F`` (``rhs``, ``stage_L``): RK4 with M
+    substeps of DT = T / M; cost "quadrature": q = sum over the substeps of DT / 6 (L1 + 2 L2 + 2 L3 + L4)
+    with L = sum W_i (z_i - zr_i)^2 at the four RK4 stage states (the input held); cost "node": q = L at
+    the node itself."""
+    h = T / M
+    x, u = list(z[:3]), list(z[3:])
+    L = lambda xs: stage_cost("unicycle", list(xs) + u, row, W, None)  # noqa: E731
+    q = L(x) if cost == "node" else None
+    for _ in range(M):
+        k1 = f_unicycle(x, u, None, row)
+        x2 = [xi + (h / 2) * ki for xi, ki in zip(x, k1)]
+        k2 = f_unicycle(x2, u, None, row)
+        x3 = [xi + (h / 2) * ki for xi, ki in zip(x, k2)]
+        k3 = f_unicycle(x3, u, None, row)
+        x4 = [xi + h * ki for xi, ki in zip(x, k3)]
+        k4 = f_unicycle(x4, u, None, row)
+        if cost == "quadrature":
+            t = (h / 6) * (L(x) + 2 * L(x2) + 2 * L(x3) + L(x4))
+            q = t if q is None else q + t
+        x = [xi + (h / 6) * (a + 2 * b + 2 * c + d) for xi, a, b, c, d in zip(x, k1, k2, k3, k4)]
+    return x, q
+
+
+def evaluate(model, z, row, W, par, T, M, cost="node"):
+    """(x+ (list of nx), q) of one stage in the arithmetic of its arguments; ``cost`` is read by the
+    unicycle alone (the ODE models have the node cost)."""
+    if model == "unicycle":
+        assert cost in ("node", "quadrature")
+        return unicycle_stage(z, row, W, T, M, cost)
+    return interval(model, z, row, par, T, M), stage_cost(model, z, row, W, par)
+
+
 # ---------------------------------------------------------------------------- the reference
-def stage_derivs(model, Z, lam, zr, fs, T, M, Q, R, par, dtype=np.longdouble):
+def stage_derivs(model, Z, lam, zr, fs, T, M, Q, R, par, dtype=np.longdouble, cost="node"):
     """Z (n, nz), lam (n, nx), zr (n, nz) stage rows -> dict of
     xf (n, nx), q (n,) unscaled, A (n, nx, nx), B (n, nx, nu), g = fs grad q (n, nz) and
-    H = fs hess q + hess(lam^T F) (n, nz (nz + 1) / 2) packed in ``symix`` order, all in ``dtype``."""
+    H = fs hess q + hess(lam^T F) (n, nz (nz + 1) / 2) packed in ``symix`` order, all in ``dtype``.
+    ``cost``: the unicycle's "node" or "quadrature" (``evaluate``)."""
     nx, nu = NXU[model]
     nz = nx + nu
     Z, lam, zr = (np.asarray(v, dtype=dtype) for v in (Z, lam, zr))
@@ -219,8 +261,7 @@ def stage_derivs(model, Z, lam, zr, fs, T, M, Q, R, par, dtype=np.longdouble):
     for m in range(nz):
         for nn in range(m, nz):
             zs = [HD(zc[i], one if i == m else zero, one if i == nn else zero, zero) for i in range(nz)]
-            xs = interval(model, zs, row, par, T, M)
-            qs = stage_cost(model, zs, row, W, par)
+            xs, qs = evaluate(model, zs, row, W, par, T, M, cost)
             h = fs * qs.ab
             for r in range(nx):
                 h = h + lam[:, r] * xs[r].ab
