@@ -557,6 +557,77 @@ int mpcx_sens_weights_vjp(mpcx_handle* h, int32_t B, const double* P, const doub
                           const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
                           double* gWk, double* gW, int32_t* flag);
 
+/* The model as the sensitivity calls below see it: a stage's model row has n_th entries.
+ *   ODE models: the leading entries of mpcx_spec.par that the model reads --
+ *     MPCX_MODEL_KIN_BICYCLE 1 (L), MPCX_MODEL_DYN_BICYCLE 5 (m, a, b, Ca, Jz), MPCX_MODEL_CARTPOLE 5 (M, m, L, g, c),
+ *     MPCX_MODEL_PATH_BICYCLE 4 (L, c1, c2, w_z; L and w_z enter its cost, c1 and c2 its dynamics).
+ *   MPCX_MODEL_LINEAR: nx nx + nx nu + nx, the stage's tables (A row-major, B row-major, c) in
+ *     mpcx_set_linear_model's layout, nx and nu of the handle.
+ *   MPCX_MODEL_UNICYCLE: 0.  It has no constants; mpcx_set_par and the four sensitivity calls below return
+ *     MPCX_EINVAL for it. */
+int mpcx_model_dims(const mpcx_handle* h, int32_t* n_th);
+
+/* Replace the constants par[0..n_th) of an ODE model's handle; host only, nothing is launched.  Every later
+ * launch uses them, with results bit-identical to those of a handle created with these constants in its spec (a
+ * launch takes them from the spec each time; nothing else keeps them).  MPCX_EINVAL, the handle unchanged:
+ * MPCX_MODEL_LINEAR (its constants are its tables: mpcx_set_linear_model), MPCX_MODEL_UNICYCLE (none), a NULL
+ * argument, an entry that is not finite, and for MPCX_MODEL_PATH_BICYCLE L = par[0] <= 0, as mpcx_create. */
+int mpcx_set_par(mpcx_handle* h, const double* par);
+
+/* Directional sensitivities of the solution to the model at a primal-dual point as a solve returns it:
+ * dw = (dw* / dmodel) dTh for m directions of the model rows.  One launch, no solve; no reference counterpart --
+ * it replaces central differences of whole solves on handles with perturbed constants or tables.  The KKT matrix
+ * is that of mpcx_sens_x0 (H_k + Sigma_k, A_k, B_k, stage 0 at (x0, U_0), P_N = Sigma_x).  A model row th_k enters
+ * the interval map F_k(z, th) and, for MPCX_MODEL_PATH_BICYCLE, the stage cost q_k(z, th).  Stationarity and
+ * the defect of stage k are grad_z q_k + grad_z (lam_{k+1}^T F_k) - (lam_k; 0) = 0 and F_k - x_{k+1} = 0, so along
+ * dTh_k, the multipliers held fixed, per stage k < N
+ *   r_k = [d(grad_z q_k)/dth + d(grad_z (lam_{k+1}^T F_k))/dth] dTh_k,    d_k = (dF_k/dth) dTh_k,
+ * dX_0 = 0, nothing on node N, and the linear system reads K (dz; dlam) + (r; d) = 0.  ODE models: r_k and d_k
+ * come from hyper-dual RK4 passes with the constants seeded (exact: no truncation), nz passes per direction;
+ * the 6-state bicycle runs its hyper-dual dynamics here.  MPCX_MODEL_LINEAR, closed form:
+ *   d_k = dA_k x_k + dB_k u_k + dc_k  (x_0 = P[:nx]),    r_k = (dA_k^T lam_{k+1}; dB_k^T lam_{k+1}).
+ * The solve is mpcx_sens_p's (Riccati solve of right-hand sides, one step of iterative refinement).  These are
+ * barrier-problem sensitivities, as mpcx_sens_x0's.
+ *   dTh    B x m x (per_stage ? N : 1) x n_th, 1 <= m <= nx per call: one row per stage, or (per_stage = 0) one
+ *          row used at every stage (an ODE model's par); a row that is the same at every stage gives the same
+ *          bits either way.  Exact: a zero direction gives zeros.
+ *   dw     B x n_w x m, mpcx_sens_p's layout (the X_0 rows are exact zeros).  A column's bits do not depend on
+ *          the other columns or on m, nor an instance's on the batch it is in.
+ *   flag   as mpcx_sens_p.
+ * Bounds in force: as mpcx_sens_x0.  MPCX_EINVAL, with nothing launched: a NULL handle, B <= 0, a NULL pointer
+ * other than lbw / ubw / flag, MPCX_MODEL_UNICYCLE (n_th = 0), m outside 1..nx, N >= 64.  The device variant
+ * only enqueues one launch on `stream`: it never synchronises, allocates nothing and can be captured in a graph. */
+int mpcx_sens_model_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                        const double* d_lam_x, const double* d_dTh, int32_t per_stage, int32_t m, double* d_dw,
+                        int32_t* d_flag, void* stream);
+int mpcx_sens_model(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                    const double* lam_x, const double* lbw, const double* ubw, const double* dTh, int32_t per_stage,
+                    int32_t m, double* dw, int32_t* flag);
+
+/* Reverse mode of mpcx_sens_model: the gradients of a scalar loss on the solution with respect to every stage's
+ * model row, and their sum over the stages, for m cotangents g shaped like w, from one launch.  K is symmetric
+ * and the adjoint solve is mpcx_sens_vjp's, K (z~; lam~) + (g; 0) = 0 (rq_k = gX_k on every node, rr_k = gU_k,
+ * d = 0, zero start, one refinement step), with lam~_k = P_k X~_k + p~_k its costates; lam~_{k+1} is the unknown
+ * paired with stage k's defect row.  Then, no sign flipped,
+ *   <g, dw> = sum_{k<N} (z~_k^T r_k + lam~_{k+1}^T d_k),
+ *   gThk_k = (dr_k/dth_k)^T z~_k + (dd_k/dth_k)^T lam~_{k+1},
+ * and <g, dw> = <gThk, dTh> for dw = mpcx_sens_model(dTh, per_stage = 1), to rounding.  ODE models: n_th nz
+ * hyper-dual passes per instance and stage.  MPCX_MODEL_LINEAR: gA_k = lam~_{k+1} x_k^T + lam_{k+1} X~_k^T,
+ * gB_k likewise with u_k and U~_k, gc_k = lam~_{k+1}.  gTh = sum_k gThk_k is the gradient for a row shared by
+ * all stages: for the ODE models, with respect to the handle's par.
+ *   gw     B x m x n_w, 1 <= m <= nx per call
+ *   gThk   B x m x N x n_th or NULL;  gTh  B x m x n_th or NULL; one of them is required.  Every entry of those
+ *          given is written, NaN throughout for an irregular instance.  A cotangent's bits do not depend on the
+ *          others or on m, nor an instance's on its batch; a zero cotangent gives zeros.
+ *   flag   as mpcx_sens_p.
+ * Bounds, refusals and the device variant: as mpcx_sens_model. */
+int mpcx_sens_model_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                            const double* d_lam_x, const double* d_gw, int32_t m, double* d_gThk, double* d_gTh,
+                            int32_t* d_flag, void* stream);
+int mpcx_sens_model_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                        const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
+                        double* gThk, double* gTh, int32_t* flag);
+
 #ifdef __cplusplus
 }
 #endif

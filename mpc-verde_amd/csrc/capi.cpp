@@ -1393,6 +1393,164 @@ int mpcx_sens_weights_vjp(mpcx_handle* h, int32_t B, const double* P, const doub
   return 0;
 }
 
+int mpcx_model_dims(const mpcx_handle* h, int32_t* n_th) {
+  if (!h) return fail(MPCX_EINVAL, "null handle");
+  const mpcx::ModelOps* ops = handle_ops(h);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  if (n_th) *n_th = ops->n_th;
+  return 0;
+}
+
+int mpcx_set_par(mpcx_handle* h, const double* par) {
+  if (!h || !par) return fail(MPCX_EINVAL, "null argument");
+  if (!is_ode(h->spec.model))
+    return fail(MPCX_EINVAL, h->spec.model == MPCX_MODEL_LINEAR
+                                 ? "set_par: the linear model's constants are its tables (mpcx_set_linear_model)"
+                                 : "set_par: the unicycle has no model constants (n_th = 0)");
+  const mpcx::ModelOps* ops = handle_ops(h);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  for (int i = 0; i < ops->n_th; ++i)
+    if (!std::isfinite(par[i])) return fail(MPCX_EINVAL, "set_par: the constants must be finite");
+  if (h->spec.model == MPCX_MODEL_PATH_BICYCLE && !(par[0] > 0))
+    return fail(MPCX_EINVAL, "path bicycle: L = par[0] must be > 0");
+  for (int i = 0; i < ops->n_th; ++i) h->spec.par[i] = par[i];  // (every launch takes its constants from the spec)
+  return 0;
+}
+
+// what the four model-sensitivity entry points refuse before anything is launched
+static int check_sens_model_args(const mpcx_handle* h, int B, const char* who, bool ptrs, int m) {
+  auto say = [&](const char* what) { return fail(MPCX_EINVAL, std::string(who) + ": " + what); };
+  if (!h) return fail(MPCX_EINVAL, "null handle");
+  if (B <= 0) return say("B must be >= 1");
+  if (!ptrs) return say("P, w, lam_g, lam_x, the directions or cotangents and an output are required");
+  if (h->spec.model == MPCX_MODEL_UNICYCLE) return say("the unicycle has no model constants (n_th = 0)");
+  if (m < 1 || m > h->spec.nx) return say("m must be between 1 and nx columns per call");
+  if (h->spec.N >= 64) return say("horizons N >= 64 (lane groups wider than a wavefront) are not supported");
+  if (int r = check_model_ready(h, B)) return r;
+  return 0;
+}
+
+int mpcx_sens_model_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                        const double* d_lam_x, const double* d_dTh, int32_t per_stage, int32_t m, double* d_dw,
+                        int32_t* d_flag, void* stream) {
+  if (int r = check_sens_model_args(h, B, "sens_model", d_P && d_w && d_lam_g && d_lam_x && d_dTh && d_dw, m)) return r;
+  if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_mdl(a, d_w, d_lam_g, d_lam_x, d_dTh, per_stage, m, d_dw, d_flag, (hipStream_t)stream));
+  return 0;
+}
+
+int mpcx_sens_model(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                    const double* lam_x, const double* lbw, const double* ubw, const double* dTh, int32_t per_stage,
+                    int32_t m, double* dw, int32_t* flag) {
+  if (int r = check_sens_model_args(h, B, "sens_model", P && w && lam_g && lam_x && dTh && dw, m)) return r;
+  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  if (int r = ensure(h, B)) return r;
+  hipStream_t s = h->stream;
+  const mpcx::ModelOps* hops = handle_ops(h);
+  if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
+  const size_t n_dw = (size_t)B * h->nw * m, n_d = (size_t)B * m * (per_stage ? h->spec.N : 1) * hops->n_th;
+  if (n_dw + n_d > h->cap_sens) {
+    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
+    dev_free(h->d_sens);
+    h->cap_sens = 0;
+    HIPCHK(hipMalloc(&h->d_sens, (n_dw + n_d) * sizeof(double)));
+    h->cap_sens = n_dw + n_d;
+  }
+  int call_xbnd = 0;
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
+  double *d_dw = h->d_sens, *d_d = h->d_sens + n_dw;
+  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_d, dTh, n_d * sizeof(double), hipMemcpyHostToDevice, s));
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_mdl(a, h->d_w, h->d_lam, h->d_lamx, d_d, per_stage, m, d_dw, h->d_status, s));
+  HIPCHK(hipMemcpyAsync(dw, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mpcx_sens_model_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                            const double* d_lam_x, const double* d_gw, int32_t m, double* d_gThk, double* d_gTh,
+                            int32_t* d_flag, void* stream) {
+  if (int r = check_sens_model_args(h, B, "sens_model_vjp",
+                                    d_P && d_w && d_lam_g && d_lam_x && d_gw && (d_gThk || d_gTh), m))
+    return r;
+  if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_mdl_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gThk, d_gTh, d_flag, (hipStream_t)stream));
+  return 0;
+}
+
+int mpcx_sens_model_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                        const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
+                        double* gThk, double* gTh, int32_t* flag) {
+  if (int r = check_sens_model_args(h, B, "sens_model_vjp", P && w && lam_g && lam_x && gw && (gThk || gTh), m))
+    return r;
+  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  if (int r = ensure(h, B)) return r;
+  hipStream_t s = h->stream;
+  const mpcx::ModelOps* hops = handle_ops(h);
+  if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
+  const size_t n_g = (size_t)B * m * h->nw, n_s = (size_t)B * m * hops->n_th, n_k = n_s * h->spec.N;
+  if (n_g + n_s + n_k > h->cap_sens) {
+    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
+    dev_free(h->d_sens);
+    h->cap_sens = 0;
+    HIPCHK(hipMalloc(&h->d_sens, (n_g + n_s + n_k) * sizeof(double)));
+    h->cap_sens = n_g + n_s + n_k;
+  }
+  int call_xbnd = 0;
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
+  double *d_gw = h->d_sens, *d_gs = d_gw + n_g, *d_gk = d_gs + n_s;
+  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_gw, gw, n_g * sizeof(double), hipMemcpyHostToDevice, s));
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(ops->sens_mdl_vjp(a, h->d_w, h->d_lam, h->d_lamx, d_gw, m, gThk ? d_gk : nullptr, gTh ? d_gs : nullptr,
+                           h->d_status, s));
+  if (gThk) HIPCHK(hipMemcpyAsync(gThk, d_gk, n_k * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (gTh) HIPCHK(hipMemcpyAsync(gTh, d_gs, n_s * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
 int mpcx_rk4_sens_dev(mpcx_handle* h, int32_t B, const double* d_X, const double* d_U, const double* d_xr,
                       double* d_J, void* stream) {
   if (!h || !d_X || !d_U || !d_xr || !d_J) return fail(MPCX_EINVAL, "null argument");

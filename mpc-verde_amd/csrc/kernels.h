@@ -2489,6 +2489,43 @@ static hipError_t launch_sens_wt_vjp_model(const SolveArgs& a, const double* W, 
   return hipGetLastError();
 }
 
+// sensitivities to the model row (sens.h sens_mdl_kernel, sens_mdl_vjp_kernel): the same lane groups;
+// m directions / cotangents per instance, 1 <= m <= NX; a model row has Model::NTH entries (none: no launch)
+template <class Model>
+static hipError_t launch_sens_mdl_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
+                                        const double* DTH, int per_stage, int m, double* DW, int32_t* FLAG,
+                                        hipStream_t stream) {
+  if constexpr (Model::NTH == 0) {
+    return hipErrorInvalidValue;
+  } else {
+    if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
+    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+    const int blocks = (int)(((long)a.B * G + 63) / 64);
+    const int ps = per_stage ? 1 : 0;
+    if (G == 16) hipLaunchKernelGGL((sens_mdl_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DTH, ps, m, DW, FLAG);
+    else if (G == 32) hipLaunchKernelGGL((sens_mdl_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DTH, ps, m, DW, FLAG);
+    else hipLaunchKernelGGL((sens_mdl_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DTH, ps, m, DW, FLAG);
+    return hipGetLastError();
+  }
+}
+
+template <class Model>
+static hipError_t launch_sens_mdl_vjp_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
+                                            const double* GW, int m, double* GTK, double* GTS, int32_t* FLAG,
+                                            hipStream_t stream) {
+  if constexpr (Model::NTH == 0) {
+    return hipErrorInvalidValue;
+  } else {
+    if (a.N >= 64 || m < 1 || m > Model::NX || (!GTK && !GTS)) return hipErrorInvalidValue;
+    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
+    const int blocks = (int)(((long)a.B * G + 63) / 64);
+    if (G == 16) hipLaunchKernelGGL((sens_mdl_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GTK, GTS, FLAG);
+    else if (G == 32) hipLaunchKernelGGL((sens_mdl_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GTK, GTS, FLAG);
+    else hipLaunchKernelGGL((sens_mdl_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GTK, GTS, FLAG);
+    return hipGetLastError();
+  }
+}
+
 #ifdef MPCX_STAMPS
 // diagnostic build: this unit's setters of its own copies of the stamp/counter pointers
 static int diag_set_stamps(void* d) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mpcx_stamps), &d, sizeof(void*)); }
@@ -2523,6 +2560,9 @@ static ModelOps model_ops_of(const char* name) {
                   Model::NWT,
                   launch_sens_wt_model<Model>,
                   launch_sens_wt_vjp_model<Model>,
+                  Model::NTH,
+                  launch_sens_mdl_model<Model>,
+                  launch_sens_mdl_vjp_model<Model>,
   };
 }
 

@@ -162,6 +162,8 @@ struct UnicycleModel {
       }
     }
   }
+  // The model row of a stage (sens.h sens_mdl_kernel): the unicycle has no constants, so no such launch.
+  static constexpr int NTH = 0;
   // The weight row of a stage: (Q_0..Q_2, R_0, R_1).
   static constexpr int NWT = 5;
   // Weight tangent of a stage (sens.h sens_wt_kernel; no solve kernel calls it): r = d(grad_z q)/d(Q, R) . dwt
@@ -409,6 +411,48 @@ struct LinearModel {
         for (int j = i; j < NZ; ++j)
           gwt[symix(i, j, NZ) * NX + col] = (i == j) ? 2.0 * zt[i] * dz[i] : 2.0 * fma(zt[i], dz[j], zt[j] * dz[i]);
     }
+  }
+  // The model row of a stage: its tables (A row-major NX NX, B row-major NX NU, c NX), in that order.
+  static constexpr int NTH = NX * NX + NX * NU + NX;
+  // model tangent (OdeModel::model_tangent) in closed form: d = dA x + dB u + dc at the stage's evaluation
+  // point (stage 0: x0), r = (dA^T ln; dB^T ln); the cost reads none of them
+  __device__ __forceinline__ static void model_tangent(const ModelArgs&, const Ctx&, const double* z, const double* ln,
+                                                       const double* dth, double* r, double* d) {
+    const double *dA = dth, *dB = dth + NX * NX, *dc = dth + NX * NX + NX * NU;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      double e = dc[i];
+#pragma unroll
+      for (int m = 0; m < NX; ++m) e = fma(dA[i * NX + m], z[m], e);
+#pragma unroll
+      for (int l = 0; l < NU; ++l) e = fma(dB[i * NU + l], z[NX + l], e);
+      d[i] = e;
+    }
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      double e = 0.0;
+#pragma unroll
+      for (int m = 0; m < NX; ++m) e = fma(i < NX ? dA[m * NX + i] : dB[m * NU + (i - NX)], ln[m], e);
+      r[i] = e;
+    }
+  }
+  // model cotangent (OdeModel::model_cotangent): gA[r][m] = lam~_r z_m + ln_r z~_m, gB likewise on the
+  // inputs, gc = lam~, NX columns (gth: NTH x NX)
+  __device__ __forceinline__ static void model_cotangent(const ModelArgs&, const Ctx&, const double* z, const double* ln,
+                                                         const double* xt, const double* ut, const double* lt,
+                                                         double* gth) {
+#pragma unroll
+    for (int col = 0; col < NX; ++col)
+#pragma unroll
+      for (int r = 0; r < NX; ++r) {
+        const double l = lt[r * NX + col];
+#pragma unroll
+        for (int m = 0; m < NX; ++m) gth[(r * NX + m) * NX + col] = fma(l, z[m], ln[r] * xt[m * NX + col]);
+#pragma unroll
+        for (int m = 0; m < NU; ++m)
+          gth[(NX * NX + r * NU + m) * NX + col] = fma(l, z[NX + m], ln[r] * ut[m * NX + col]);
+        gth[(NX * NX + NX * NU + r) * NX + col] = l;
+      }
   }
 };
 

@@ -202,8 +202,9 @@ struct KinBicycle {
   static constexpr unsigned INDEP = (1u << 0) | (1u << 1);               // f does not read X, Y
   static constexpr int kTrigPerEval = 2, kTrigInput = 1, kTrigMaxM = 1;  // sincos(psi); tan(delta)
   static constexpr bool kAdjoint = false;  // derivatives by hyper-dual passes (OdeModel::derivs)
-  template <class S, class Tc>
-  __device__ __forceinline__ static void f(const S* x, const S* u, const double* par, S* dx, Tc& tc) {
+  static constexpr int NTH = 1;  // the model row (sens.h sens_mdl_kernel): par[0..NTH) = (L)
+  template <class S, class Pt, class Tc>
+  __device__ __forceinline__ static void f(const S* x, const S* u, const Pt* par, S* dx, Tc& tc) {
     S sp, cp;
     tc.sincos_x(x[2], sp, cp);
     dx[0] = u[0] * cp;
@@ -224,10 +225,11 @@ struct DynBicycle {
   // change, N = 50, alternating builds): 459-476 -> 258-261 us per IPM iteration, 136 k -> 337 k
   // solves/s in 10-step launches, lock-step 85 k -> 125 k, against the hyper-dual passes
   static constexpr bool kAdjoint = true;
-  template <class S, class Tc>
-  __device__ __forceinline__ static void f(const S* x, const S* u, const double* par, S* dx, Tc& tc) {
+  static constexpr int NTH = 5;  // the model row: (m, a, b, Ca, Jz)
+  template <class S, class Pt, class Tc>
+  __device__ __forceinline__ static void f(const S* x, const S* u, const Pt* par, S* dx, Tc& tc) {
     // par = (m, a, b, Ca, Jz): Trajectory_tracking_dynamic_model.py:36-40 (a, b = CG-axle distances)
-    const double m = par[0], a = par[1], b = par[2], Ca2 = 2.0 * par[3], Jz = par[4];
+    const Pt m = par[0], a = par[1], b = par[2], Ca2 = 2.0 * par[3], Jz = par[4];
     const S psi = x[2], vx = x[3], vy = x[4], r = x[5], d = u[0];
     S sp, cp, sd, cd;
     tc.sincos_x(psi, sp, cp);
@@ -350,10 +352,11 @@ struct CartPole {
   static constexpr unsigned INDEP = (1u << 0);                                        // f does not read p
   static constexpr int kTrigPerEval = 3, kTrigInput = 0, kTrigMaxM = 1;  // sincos(phi), 1/(M + m sin^2 phi)
   static constexpr bool kAdjoint = false;
-  template <class S, class Tc>
-  __device__ __forceinline__ static void f(const S* x, const S* u, const double* par, S* dx, Tc& tc) {
+  static constexpr int NTH = 5;  // the model row: (M, m, L, g, c)
+  template <class S, class Pt, class Tc>
+  __device__ __forceinline__ static void f(const S* x, const S* u, const Pt* par, S* dx, Tc& tc) {
     // par = (M, m, L, g, c); phi measured so that the upright linearisation is the reference's Ac
-    const double Mc = par[0], m = par[1], L = par[2], g = par[3], c = par[4];
+    const Pt Mc = par[0], m = par[1], L = par[2], g = par[3], c = par[4];
     S s, co;
     tc.sincos_x(x[2], s, co);
     const S pdd = tc.div_x(u[0] - c * x[1] - (m * L) * (x[3] * x[3]) * s + (m * g) * (s * co), Mc + m * (s * s));
@@ -388,9 +391,11 @@ struct PathBicycle {
   static constexpr bool kStagePar = true;  // f reads the stage row
   static constexpr bool kCostHook = true;  // cost_ref / cost_extra / cost_extra_derivs
   static constexpr int kCarried = 1;       // the last state is carried, not integrated
-  template <class S, class Tc>
-  __device__ __forceinline__ static void f(const S* x, const S* u, const double* par, const double* zr, S* dx, Tc& tc) {
-    const double c1 = par[1], c2 = par[2], yt = zr[0], phit = zr[1], kap = zr[3];
+  static constexpr int NTH = 4;  // the model row: (L, c1, c2, w_z); L and w_z enter the cost hook only
+  template <class S, class Pt, class Tc>
+  __device__ __forceinline__ static void f(const S* x, const S* u, const Pt* par, const double* zr, S* dx, Tc& tc) {
+    const Pt c1 = par[1], c2 = par[2];
+    const double yt = zr[0], phit = zr[1], kap = zr[3];
     S se, ce;
     tc.sincos_x(x[1] - phit, se, ce);
     const S iden = tc.recip_x(1.0 - (x[0] - yt) * kap);
@@ -428,6 +433,13 @@ struct PathBicycle {
     H[symix(3, 3, NX + NU)] += h1;
     H[symix(3, 4, NX + NU)] += h1;
     H[symix(4, 4, NX + NU)] += h1;
+  }
+  // the hook's term alone on scalars of any type, the constants included (OdeModel::model_tangent seeds
+  // both as hyper-dual numbers; no solve kernel calls it): w_z (tan(s + d) - L kappa)^2
+  template <class S, class Pt>
+  __device__ __forceinline__ static S cost_extra_term(const Pt* par, const double* zr, const S* z) {
+    const S r = tan(z[3] + z[4]) - par[0] * zr[3];
+    return par[3] * (r * r);
   }
 };
 
@@ -485,6 +497,42 @@ __device__ __forceinline__ void ode_rk4(const S* x0, const S* u, const OdeParams
         Dyn::f(xt, u, op.par, k, tc);
       const double wa = (st == 0 || st == 3) ? 1.0 : 2.0;  // k1 + 2 k2 + 2 k3 + k4
       const double cn = (st == 2) ? h : 0.5 * h;           // next stage point x + c k
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        acc[i] = st == 0 ? k[i] : acc[i] + wa * k[i];
+        xt[i] = x[i] + cn * k[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = x[i] + (h / 6.0) * acc[i];
+  }
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xf[i] = x[i];
+}
+
+// The same RK4 with the model constants handed in as scalars of their own type (the model-row
+// sensitivities of sens.h seed them as hyper-dual numbers; no solve kernel calls it).  A copy, not a
+// call from ode_rk4: the solve units' code is then, instruction for instruction, what it was.
+template <class Dyn, class S, class Pt, class Tc>
+__device__ __forceinline__ void ode_rk4_par(const S* x0, const S* u, double h, int M, const Pt* par, S* xf, Tc& tc,
+                                            const double* zr) {
+  constexpr int NX = Dyn::NX - CarriedOf<Dyn>::value;
+  S x[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) x[i] = x0[i];
+#pragma unroll 1
+  for (int s = 0; s < M; ++s) {
+    S acc[NX], xt[NX], k[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xt[i] = x[i];
+#pragma unroll 1
+    for (int st = 0; st < 4; ++st) {
+      if constexpr (StageParOf<Dyn>::value)
+        Dyn::f(xt, u, par, zr, k, tc);
+      else
+        Dyn::f(xt, u, par, k, tc);
+      const double wa = (st == 0 || st == 3) ? 1.0 : 2.0;
+      const double cn = (st == 2) ? h : 0.5 * h;
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
         acc[i] = st == 0 ? k[i] : acc[i] + wa * k[i];
@@ -686,6 +734,99 @@ struct OdeModel {
       const double e = z[i] - ref(c, i);
 #pragma unroll
       for (int col = 0; col < NX; ++col) gwt[i * NX + col] = 2.0 * (i < NX ? xt[i * NX + col] : ut[(i - NX) * NX + col]) * e;
+    }
+  }
+  // The model row of a stage (sens.h sens_mdl_kernel): the leading NTH constants of par, the ones the model reads.
+  static constexpr int NTH = Dyn::NTH;
+  // the interval map on hyper-dual numbers with the constants hyper-dual too (interval() with par of the
+  // scalar type; every model goes through its hyper-dual f here, the 6-state bicycle included)
+  __device__ __forceinline__ static void interval_par(const ModelArgs& a, const Ctx& c, const HD* z, const HD* par, HD* xf) {
+    TrigDirect td;
+    if constexpr (kCarried > 0) {
+      HD ue[NU];
+      Dyn::eff_input(z, ue);
+      ode_rk4_par<Dyn, HD, HD>(z, ue, a.op.h, a.op.M, par, xf, td, c.zr);
+      Dyn::carry(ue, xf);
+    } else {
+      ode_rk4_par<Dyn, HD, HD>(z, z + NX, a.op.h, a.op.M, par, xf, td, c.zr);
+    }
+  }
+  // Model tangent of a stage (sens.h sens_mdl_kernel; no solve kernel calls it): along a direction dth of the
+  // model row, at fs = 1 and with the multiplier ln of the stage's defect held fixed,
+  //   r = [d(grad_z q)/dth + d(grad_z (ln^T F))/dth] dth,    d = (dF/dth) dth.
+  // NZ hyper-dual passes, pass i seeded with (e_i of z, dth on par): xs.b is d (the b parts never meet the a
+  // seeds, so every pass forms the same bits), ln^T xs.ab the mixed term of row i; a cost hook is evaluated
+  // on the same numbers.  One RK4 body (runtime loop over the passes).  A zero direction leaves every b and
+  // ab part an exact zero.
+  __device__ __forceinline__ static void model_tangent(const ModelArgs& a, const Ctx& c, const double* z, const double* ln,
+                                                       const double* dth, double* r, double* d) {
+    HD par[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) par[i] = HD{a.op.par[i], 0.0, i < NTH ? dth[i < NTH ? i : 0] : 0.0, 0.0};
+#pragma unroll 1
+    for (int i = 0; i < NZ; ++i) {
+      HD zs[NZ], xs[NX];
+#pragma unroll
+      for (int j = 0; j < NZ; ++j) zs[j] = HD{z[j], j == i ? 1.0 : 0.0, 0.0, 0.0};
+      interval_par(a, c, zs, par, xs);
+      double s = ln[0] * xs[0].ab;
+#pragma unroll
+      for (int rr = 1; rr < NX; ++rr) s = fma(ln[rr], xs[rr].ab, s);
+      if constexpr (kCostHook) s += Dyn::cost_extra_term(par, c.zr, zs).ab;
+#pragma unroll
+      for (int j = 0; j < NZ; ++j)
+        if (j == i) r[j] = s;
+#pragma unroll
+      for (int rr = 0; rr < NX; ++rr) d[rr] = xs[rr].b;
+    }
+  }
+  // Model cotangent of a stage (sens.h sens_mdl_vjp_kernel), the transpose of model_tangent for NX columns
+  // at once (xt: NX x NX, ut: NU x NX the adjoint solution, lt: NX x NX the next node's adjoint costate;
+  // gth: NTH x NX, row = constant, column = cotangent; a column's bits do not depend on the others):
+  //   gth_j = sum_i (dr_i/dth_j) z~_i + sum_r (dd_r/dth_j) lam~_r,
+  // NTH NZ passes seeded with (e_i of z, e_j of par).  A zero cotangent meets only products with 0.
+  __device__ __forceinline__ static void model_cotangent(const ModelArgs& a, const Ctx& c, const double* z,
+                                                         const double* ln, const double* xt, const double* ut,
+                                                         const double* lt, double* gth) {
+#pragma unroll
+    for (int i = 0; i < NTH * NX; ++i) gth[i] = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < NTH; ++j) {
+      HD par[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) par[i] = HD{a.op.par[i], 0.0, i == j ? 1.0 : 0.0, 0.0};
+      double acc[NX];
+#pragma unroll
+      for (int col = 0; col < NX; ++col) acc[col] = 0.0;
+#pragma unroll 1
+      for (int i = 0; i < NZ; ++i) {
+        HD zs[NZ], xs[NX];
+#pragma unroll
+        for (int jj = 0; jj < NZ; ++jj) zs[jj] = HD{z[jj], jj == i ? 1.0 : 0.0, 0.0, 0.0};
+        interval_par(a, c, zs, par, xs);
+        double s = ln[0] * xs[0].ab;
+#pragma unroll
+        for (int rr = 1; rr < NX; ++rr) s = fma(ln[rr], xs[rr].ab, s);
+        if constexpr (kCostHook) s += Dyn::cost_extra_term(par, c.zr, zs).ab;
+#pragma unroll
+        for (int col = 0; col < NX; ++col) {
+          double zt = 0.0;
+#pragma unroll
+          for (int jj = 0; jj < NZ; ++jj)
+            if (jj == i) zt = jj < NX ? xt[jj * NX + col] : ut[(jj - NX) * NX + col];
+          acc[col] = fma(s, zt, acc[col]);
+        }
+        if (i == NZ - 1)
+#pragma unroll
+          for (int col = 0; col < NX; ++col)
+#pragma unroll
+            for (int rr = 0; rr < NX; ++rr) acc[col] = fma(xs[rr].b, lt[rr * NX + col], acc[col]);
+      }
+#pragma unroll
+      for (int jj = 0; jj < NTH; ++jj)
+        if (jj == j)
+#pragma unroll
+          for (int col = 0; col < NX; ++col) gth[jj * NX + col] = acc[col];
     }
   }
   // Exact derivatives by forward sensitivities and stage adjoints (Dyn::kAdjoint: closed-form

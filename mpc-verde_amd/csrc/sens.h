@@ -24,7 +24,10 @@
 // sens_vjp_kernel, the transpose: the gradient of a loss on w for the whole row.
 // sens_bnd_kernel and sens_bnd_vjp_kernel are the same pair for directions of the
 // box bounds lbw / ubw, for every model; sens_wt_kernel and sens_wt_vjp_kernel for
-// directions of the cost weights, through the models' weight_tangent / weight_cotangent hooks.
+// directions of the cost weights, through the models' weight_tangent / weight_cotangent hooks; sens_mdl_kernel
+// and sens_mdl_vjp_kernel for directions of the model itself -- the ODE models' constants,
+// the linear model's stage tables -- through model_tangent / model_cotangent: the first right-hand side with a
+// defect term.
 // Included by kernels.h.
 #pragma once
 
@@ -1374,6 +1377,241 @@ __global__ __launch_bounds__(64) void sens_wt_vjp_kernel(SolveArgs a, const doub
           double* gs = GWS + ((size_t)inst * m + c) * NWT;
 #pragma unroll
           for (int i = 0; i < NWT; ++i) gs[i] = regular ? gwt[i * NX + c] : nan;
+        }
+  }
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Sensitivities to the model: the constants par of the ODE models, the stage tables
+// (A, B, c) of the linear model.  A model row th_k of stage k enters F_k(z, th) and, where a cost hook reads
+// the constants (the path-frame bicycle), q_k(z, th).  Stationarity and the defect of stage k read
+//   grad_z q_k + grad_z (lam_{k+1}^T F_k) - (lam_k; 0) = 0,     F_k - x_{k+1} = 0,
+// so along a direction dth_k, with the multipliers held fixed, the right-hand sides of sens_p_kernel's system are
+//   r_k = [d(grad_z q_k)/dth + d(grad_z (lam_{k+1}^T F_k))/dth] dth_k,    d_k = (dF_k/dth) dth_k
+// (Model::model_tangent), dX_0 = 0, nothing on node N: the first right-hand side with Dd != 0.
+// The transpose (sens_mdl_vjp_kernel): the KKT matrix K of the unknowns (z, lam) is symmetric and both solves are
+// K y + rhs = 0, so with (z~, lam~) the adjoint solve of sens_vjp_kernel (rq_k = gX_k, rr_k = gU_k, d = 0) and
+// lam~_k = P_k X~_k + p~_k its costates -- lam~_{k+1} is the unknown paired with the defect row of stage k --
+//   <g, dw> = sum_{k<N} (z~_k^T r_k + lam~_{k+1}^T d_k),
+//   gth_k = (dr_k/dth_k)^T z~_k + (dd_k/dth_k)^T lam~_{k+1}      (Model::model_cotangent),
+// no sign flipped; their sum over the stages is the gradient for a row shared by all stages (the handle's par).
+// A model row has Model::NTH entries.
+
+// W, LG, LX: the point, as for sens_kernel; DTH: B x m x (per_stage ? N : 1) x NTH directions of the model
+// row, one per stage or one used at every stage (launch-uniform; the same bits either way for a row that is
+// the same at every stage); DW: B x nw x m (sens_p_kernel's layout, the X_0 rows exact zeros); FLAG: B or
+// null (sens_kernel's).  1 <= m <= NX.
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_mdl_kernel(SolveArgs a, const double* __restrict__ W,
+                                                      const double* __restrict__ LG, const double* __restrict__ LX,
+                                                      const double* __restrict__ DTH, int per_stage, int m,
+                                                      double* __restrict__ DW, int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX, NTH = Model::NTH;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+
+  // ---- right-hand sides, one column per direction: the stage's model tangent at its evaluation point
+  const size_t rows = per_stage ? (size_t)N : 1, row = per_stage ? (size_t)k : 0;
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int i = 0; i < NN; ++i) Rq[i] = Dd[i] = X[i] = pk[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < NU * NX; ++i) Rr[i] = U[i] = 0.0;
+#pragma unroll 1
+  for (int c = 0; c < m; ++c) {  // (one body for the columns: the ODE models' tangent is NZ hyper-dual passes)
+    double r[NZ] = {}, d[NX] = {};
+    if (hasU) {  // (the hooks exchange nothing between lanes)
+      const double* dr = DTH + (((size_t)inst * m + c) * rows + row) * NTH;
+      double dth[NTH];
+#pragma unroll
+      for (int i = 0; i < NTH; ++i) dth[i] = dr[i];
+      Model::model_tangent(ma, s.ctx, s.ze, s.ln, dth, r, d);
+    }
+#pragma unroll
+    for (int cc = 0; cc < NX; ++cc)
+      if (cc == c) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+          Rq[i * NX + cc] = hasU ? r[i] : 0.0;
+          Dd[i * NX + cc] = hasU ? d[i] : 0.0;
+        }
+#pragma unroll
+        for (int l = 0; l < NU; ++l) Rr[l * NX + cc] = hasU ? r[NX + l] : 0.0;
+      }
+  }
+
+  // ---- the Riccati solve of the right-hand sides and one step of iterative refinement, as sens_p_kernel
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  // ---- regular: as sens_p_kernel
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  double* dw = DW + (size_t)(valid ? inst : 0) * nw * m;
+  if (hasX)
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)ixw<NX, NU>(k, i) * m + c] = regular ? X[i * NX + c] : nan;
+  if (hasU)
+    for (int l = 0; l < NU; ++l)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) dw[(size_t)iuw<NX, NU>(k, l) * m + c] = regular ? U[l * NX + c] : nan;
+  if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;
+}
+
+// W, LG, LX: the point, as for sens_kernel; GW: B x m x nw cotangents shaped like w; GTK: B x m x N x NTH
+// gradient rows with respect to every stage's own model row, or null; GTS: B x m x NTH, their sum over the
+// stages (gsum: the same bits whichever lane writes; lane 0 does), or null; every entry of the ones given is
+// written, NaN throughout for an irregular instance; FLAG: B or null.  1 <= m <= NX.  The regular test is
+// sens_vjp_kernel's: the adjoint solution and the costates the outputs are formed from.
+template <class Model, int G>
+__global__ __launch_bounds__(64) void sens_mdl_vjp_kernel(SolveArgs a, const double* __restrict__ W,
+                                                          const double* __restrict__ LG, const double* __restrict__ LX,
+                                                          const double* __restrict__ GW, int m,
+                                                          double* __restrict__ GTK, double* __restrict__ GTS,
+                                                          int32_t* __restrict__ FLAG) {
+  static_assert(G == 16 || G == 32 || G == 64, "single-wave groups");
+  constexpr int NX = Model::NX, NU = Model::NU, NZ = NX + NU, NN = NX * NX, NTH = Model::NTH;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = (int)(gid & (G - 1));  // node of this lane
+  const int inst = (int)(gid / G);
+  const bool valid = inst < a.B;
+  const int N = a.N;
+  const int nw = NX + NZ * N;
+  const bool hasX = valid && k <= N;
+  const bool hasU = valid && k < N;
+  XWave<G> xw{nullptr, 0};
+  constexpr int kSBS = 64;
+  __shared__ double tcache[Model::kTrigSlots > 0 ? Model::kTrigSlots * kSBS : 1];
+  const ModelArgs ma = [&] {
+    ModelArgs mm = model_args(a);
+    if (Model::kTrigSlots > 0) {
+      mm.tc = tcache + threadIdx.x;
+      mm.tc_stride = kSBS;
+    }
+    return mm;
+  }();
+  SensSys<Model> s;
+  sens_factor<Model, G>(a, ma, W, LG, LX, gid, k, inst, valid, s);
+  const double* Aop = Model::jacA(s.ctx, s.A);
+  const double* Bop = Model::jacB(s.ctx, s.Bm);
+
+  // ---- right-hand sides, one column per cotangent, as sens_vjp_kernel
+  double Rq[NN], Rr[NU * NX], Dd[NN], X[NN], U[NU * NX], pk[NN];
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    double gx[NX] = {}, gu[NU] = {};
+    if (c < m) {  // (launch-uniform)
+      const double* gw = GW + ((size_t)(valid ? inst : 0) * m + c) * nw;
+      if (hasX)
+        for (int i = 0; i < NX; ++i) gx[i] = gw[ixw<NX, NU>(k, i)];
+      if (hasU)
+        for (int l = 0; l < NU; ++l) gu[l] = gw[iuw<NX, NU>(k, l)];
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      Rq[i * NX + c] = gx[i];
+      Dd[i * NX + c] = 0.0;
+      X[i * NX + c] = 0.0;
+      pk[i * NX + c] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < NU; ++l) {
+      Rr[l * NX + c] = gu[l];
+      U[l * NX + c] = 0.0;
+    }
+  }
+
+#pragma unroll 1
+  for (int round = 0; round < 2; ++round)
+    sens_refine<Model, G, true>(k, N, hasX, hasU, s.Hd, Aop, Bop, s.P, s.fac, s.Kk, s.Acl, X, U, Rq, Rr, Dd, pk);
+
+  // ---- costates lam~_k = P_k X~_k + p~_k (sens_refine's own), lam~_{k+1} from the next lane
+  double lamk[NN], Ln[NN];
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      double e = s.P[symix(i, 0, NX)] * X[c];
+#pragma unroll
+      for (int mm = 1; mm < NX; ++mm) e = fma(s.P[symix(i, mm, NX)], X[mm * NX + c], e);
+      e += pk[i * NX + c];
+      lamk[i * NX + c] = hasX ? e : 0.0;
+    }
+#pragma unroll
+  for (int i = 0; i < NN; ++i) {
+    const double ln = from_next(lamk[i]);
+    Ln[i] = hasU ? ln : 0.0;
+  }
+
+  double tot = 0.0;
+  if (hasX)
+#pragma unroll
+    for (int i = 0; i < NN; ++i) tot += fabs(X[i]) + fabs(lamk[i]);
+  if (hasU)
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) tot += fabs(U[i]);
+  const bool regular = gall<G>(s.ok && tot < INFINITY, xw);  // (tot: false for NaN and Inf)
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  // ---- contraction with the model tangent: gth_k = (dr_k/dth_k)^T z~_k + (dd_k/dth_k)^T lam~_{k+1}, all
+  //      columns; zero beyond the last stage
+  double gth[NTH * NX];
+#pragma unroll
+  for (int i = 0; i < NTH * NX; ++i) gth[i] = 0.0;
+  if (hasU) Model::model_cotangent(ma, s.ctx, s.ze, s.ln, X, U, Ln, gth);
+  if (GTK && hasU)  // every stage lane writes its own rows
+#pragma unroll
+    for (int c = 0; c < NX; ++c)
+      if (c < m) {
+        double* gk = GTK + (((size_t)inst * m + c) * N + k) * NTH;
+#pragma unroll
+        for (int i = 0; i < NTH; ++i) gk[i] = regular ? gth[i * NX + c] : nan;
+      }
+  if (GTS) {  // (launch-uniform) the stage sum: every lane ends with the same bits, lane 0 writes them
+#pragma unroll
+    for (int i = 0; i < NTH * NX; ++i) gth[i] = gsum<G>(gth[i], xw);
+    if (valid && k == 0)
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+        if (c < m) {
+          double* gs = GTS + ((size_t)inst * m + c) * NTH;
+#pragma unroll
+          for (int i = 0; i < NTH; ++i) gs[i] = regular ? gth[i * NX + c] : nan;
         }
   }
   if (valid && k == 0 && FLAG) FLAG[inst] = regular ? 0 : 1;

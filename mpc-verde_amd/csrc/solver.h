@@ -213,6 +213,17 @@ struct ModelOps {
   // per stage) and GWS (B x m x n_wt, the stage sum), either may be null but not both; FLAG as above
   hipError_t (*sens_wt_vjp)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* GW,
                             int m, double* GWK, double* GWS, int32_t* FLAG, hipStream_t stream);
+  // entries of a stage's model row (Model::NTH): the constants of par the model reads, or the stage's tables
+  // (A, B, c); 0: the model has none (the unicycle) and the two launches below return hipErrorInvalidValue
+  int n_th;
+  // directional sensitivities to the model row at the same point (sens.h sens_mdl_kernel): DTH
+  // (B x m x (per_stage ? N : 1) x n_th) directions of the model rows, 1 <= m <= nx; DW (B x nw x m); FLAG as above
+  hipError_t (*sens_mdl)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* DTH,
+                         int per_stage, int m, double* DW, int32_t* FLAG, hipStream_t stream);
+  // their transpose (sens.h sens_mdl_vjp_kernel): GW (B x m x nw) cotangents shaped like w; GTK (B x m x N x n_th,
+  // per stage) and GTS (B x m x n_th, the stage sum), either may be null but not both; FLAG as above
+  hipError_t (*sens_mdl_vjp)(const SolveArgs& a, const double* W, const double* LG, const double* LX, const double* GW,
+                             int m, double* GTK, double* GTS, int32_t* FLAG, hipStream_t stream);
   // doubles of workspace per thread (restoration + chain stash; 0: the model uses none)
   int ws_slots() const { return !resto ? 0 : RestoWs::slots(nx, nu) + (ws_stash ? chain_ws_slots(nx, nu) : 0); }
 };

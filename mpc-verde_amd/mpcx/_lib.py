@@ -43,7 +43,8 @@ EXPORTS = ("mpcx_default_spec", "mpcx_create", "mpcx_destroy", "mpcx_last_error"
            "mpcx_sens_p", "mpcx_sens_p_dev", "mpcx_sens_vjp", "mpcx_sens_vjp_dev", "mpcx_sens_bounds",
            "mpcx_sens_bounds_dev", "mpcx_sens_bounds_vjp", "mpcx_sens_bounds_vjp_dev", "mpcx_weight_dims",
            "mpcx_set_weights", "mpcx_sens_weights", "mpcx_sens_weights_dev", "mpcx_sens_weights_vjp",
-           "mpcx_sens_weights_vjp_dev")
+           "mpcx_sens_weights_vjp_dev", "mpcx_model_dims", "mpcx_set_par", "mpcx_sens_model", "mpcx_sens_model_dev",
+           "mpcx_sens_model_vjp", "mpcx_sens_model_vjp_dev")
 STEP_COLD = 1
 STEP_PRIMAL_ONLY = 2
 
@@ -168,6 +169,12 @@ def load():
     lib.mpcx_sens_weights_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]
     lib.mpcx_sens_weights_vjp.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, dp, dp, ip]
     lib.mpcx_sens_weights_vjp_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]
+    lib.mpcx_model_dims.argtypes = [H, ip]
+    lib.mpcx_set_par.argtypes = [H, dp]
+    lib.mpcx_sens_model.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, ctypes.c_int32, dp, ip]
+    lib.mpcx_sens_model_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]
+    lib.mpcx_sens_model_vjp.argtypes = [H, ctypes.c_int32, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int32, dp, dp, ip]
+    lib.mpcx_sens_model_vjp_dev.argtypes = [H, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if an export is missing
     lib.mpcx_source_hash.restype = ctypes.c_char_p
@@ -260,6 +267,24 @@ class Handle:
             self._spec.Q[i] = v
         for i, v in enumerate(R):
             self._spec.R[i] = v
+
+    def model_dims(self):
+        """Entries of a stage's model row (mpcx_model_dims)."""
+        n = ctypes.c_int32()
+        check(load().mpcx_model_dims(self._h, ctypes.byref(n)))
+        return n.value
+
+    def set_par(self, par):
+        """Replace the constants of an ODE model (mpcx_set_par); the spec mirror follows."""
+        par = np.ascontiguousarray(par, np.float64).ravel()
+        n = self.model_dims()
+        if par.size != n:
+            raise ValueError(f"set_par: expected {n} constants")
+        buf = np.zeros(8)  # (the C side reads n_th entries; refusals come from there)
+        buf[:n] = par
+        check(load().mpcx_set_par(self._h, dptr(buf)))
+        for i, v in enumerate(par):
+            self._spec.par[i] = v
 
     @property
     def spec(self):

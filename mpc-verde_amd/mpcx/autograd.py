@@ -22,7 +22,7 @@ import torch
 
 from .device import DeviceLoop
 
-__all__ = ["MPCFunction", "MPCBoundsFunction", "MPCWeightsFunction", "solve_differentiable"]
+__all__ = ["MPCFunction", "MPCBoundsFunction", "MPCWeightsFunction", "MPCParFunction", "solve_differentiable"]
 
 
 class MPCFunction(torch.autograd.Function):
@@ -189,7 +189,68 @@ class MPCWeightsFunction(torch.autograd.Function):
         return gP, gQ if ctx.needs_input_grad[1] else None, gR if ctx.needs_input_grad[2] else None, None, None
 
 
-def solve_differentiable(loop: DeviceLoop, P, irregular="nan", lbw=None, ubw=None, Q=None, R=None):
+class MPCParFunction(torch.autograd.Function):
+    """forward(P, par, loop, zero_irregular): sets the constants of the solver's ODE model from the values of
+    the tensor par (n_th,), shared by the batch (``Solver.set_par``; they stay set), then as
+    :class:`MPCFunction`.  backward: one ``loop.sens_model_vjp`` launch at the saved point; ``par.grad`` is its
+    stage sum added over the batch (an instance flagged irregular puts NaN into the sum unless
+    irregular="zero" drops its row).  Only when P requires a gradient, one ``loop.sens_vjp`` launch for
+    ``P.grad`` (so the path-frame bicycle, which has no ``sens_vjp``, works with ``par.grad`` alone).  The
+    backward differentiates at the forward's constants: when the solver's are no longer those, they are
+    set for the launches and the others are put back.
+
+    Host synchronisation: the forward reads the values of par on the host (one device-to-host copy), because
+    the constants are launch arguments, not device memory.  Nothing else waits."""
+
+    @staticmethod
+    def forward(ctx, P, par, loop, zero_irregular):
+        pv = tuple(float(v) for v in par.detach().cpu().tolist())  # (the one host read)
+        loop.solver.set_par(pv)
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)
+        with torch.cuda.stream(loop.stream):
+            loop.P.copy_(P.detach(), non_blocking=True)
+            loop.solve()
+            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
+            w = point[1].clone()
+        cur.wait_stream(loop.stream)
+        ctx.loop, ctx.zero_irregular, ctx.par = loop, zero_irregular, pv
+        ctx.save_for_backward(*point)
+        return w
+
+    @staticmethod
+    def backward(ctx, gw):
+        loop, solver = ctx.loop, ctx.loop.solver
+        point = ctx.saved_tensors
+        before = tuple(float(v) for v in solver.ocp.par)
+        moved = before != ctx.par
+        if moved:  # the forward's constants, for the launches below (launch arguments: taken at the call)
+            solver.set_par(ctx.par)
+        cur = torch.cuda.current_stream(loop.device)
+        loop.stream.wait_stream(cur)
+        gP = None
+        try:
+            with torch.cuda.stream(loop.stream):
+                g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
+                _, gs, flag = loop.sens_model_vjp(g, point=point, per_stage=False)
+                gs = gs[:, 0]
+                if ctx.needs_input_grad[0]:
+                    gP, _ = loop.sens_vjp(g, point=point)  # (the same factors: the same flag)
+                    gP = gP[:, 0]
+                if ctx.zero_irregular:
+                    bad = flag[:, None] != 0
+                    gs = torch.where(bad, torch.zeros_like(gs), gs)
+                    if gP is not None:
+                        gP = torch.where(bad, torch.zeros_like(gP), gP)
+                gpar = gs.sum(dim=0).contiguous()
+        finally:
+            if moved:
+                solver.set_par(before)
+        cur.wait_stream(loop.stream)
+        return gP, gpar if ctx.needs_input_grad[1] else None, None, None
+
+
+def solve_differentiable(loop: DeviceLoop, P, irregular="nan", lbw=None, ubw=None, Q=None, R=None, par=None):
     """Solve the loop's problems at P (B, n_p float64 device tensor, the loop's resident layout) and
     return w (B, n_w) with the backward described above.  The loop is used as it stands: its warm
     start is the one its next ``solve()`` would take, and its resident P, w, lam, lamx, status and
@@ -210,12 +271,31 @@ def solve_differentiable(loop: DeviceLoop, P, irregular="nan", lbw=None, ubw=Non
     stay set), and the backward fills ``Q.grad`` / ``R.grad`` with the stage-and-batch sum from one
     ``sens_weights_vjp`` launch; ``P.grad`` is computed only when P requires it
     (:class:`MPCWeightsFunction`).  Not together with lbw / ubw, and not for linear models, whose weights
-    are their tables (``Solver.sens_weights_vjp`` gives their gradients)."""
+    are their tables (``Solver.sens_weights_vjp`` gives their gradients).
+
+    par: None, or a float64 device tensor of shape (n_th,): the constants of the loop's ODE model, shared by the
+    batch.  The solver's constants are set from its values (one host read; they stay set), and the backward
+    fills ``par.grad`` with the stage-and-batch sum from one ``sens_model_vjp`` launch; ``P.grad`` is computed
+    only when P requires it (:class:`MPCParFunction`).  Not together with lbw / ubw or Q / R, not for the
+    unicycle, which has no constants, and not for linear models, whose constants are their tables
+    (``Solver.sens_model_vjp`` gives their gradients)."""
     if irregular not in ("nan", "zero"):
         raise ValueError('irregular: "nan" or "zero"')
     if not isinstance(P, torch.Tensor) or P.dtype != torch.float64 or tuple(P.shape) != tuple(loop.P.shape) \
             or P.device != loop.device:
         raise ValueError(f"P: expected a float64 tensor of shape {tuple(loop.P.shape)} on {loop.device}")
+    if par is not None:
+        if lbw is not None or ubw is not None or Q is not None or R is not None:
+            raise ValueError("par cannot be combined with lbw / ubw or Q / R")
+        if loop.solver.ocp.model == "linear":
+            raise ValueError("par: a linear model's constants are its tables (Solver.sens_model_vjp)")
+        if loop.solver.ocp.model == "unicycle":
+            raise ValueError("par: the unicycle has no model constants")
+        n_th = loop.solver._h.model_dims()
+        if not isinstance(par, torch.Tensor) or par.dtype != torch.float64 or tuple(par.shape) != (n_th,) \
+                or par.device != loop.device:
+            raise ValueError(f"par: expected a float64 tensor of shape ({n_th},) on {loop.device}")
+        return MPCParFunction.apply(P, par, loop, irregular == "zero")
     if Q is not None or R is not None:
         if lbw is not None or ubw is not None:
             raise ValueError("Q / R and lbw / ubw cannot be combined")

@@ -297,6 +297,59 @@ class DeviceLoop:
                                                          _ptr(gs), _ptr(flag), ctypes_void(self.stream.cuda_stream)))
         return gk, gs, flag
 
+    def sens_model(self, dTh, dw_out=None, flag_out=None, point=None):
+        """Enqueue one model-sensitivity launch (mpcx_sens_model_dev) at the loop's resident P, w, lam, lamx,
+        the solver's constants or tables and the bounds in force: dTh a float64 device tensor of m <= nx
+        directions of the model rows in the kernel's layout (n_th = ``solver._h.model_dims()`` entries: the
+        constants of ``par`` the model reads, or a linear model's (A, B, c) of the padded layout), (B, m, n_th)
+        for rows used at every stage or (B, m, N, n_th) for one row per stage, gives dw (B, n_w, m) and flag
+        (B,) int32 (1 = irregular instance, NaN outputs).  point: as :meth:`sens_vjp`.  Tensors given are
+        written in place, the others are allocated; returns (dw, flag) without waiting for the stream."""
+        nw, nx, N, n_th = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.model_dims()
+        if not isinstance(dTh, torch.Tensor) or dTh.dim() not in (3, 4) or not 1 <= dTh.shape[1] <= nx:
+            raise ValueError(f"dTh: expected a ({self.B}, m, {n_th}) or ({self.B}, m, {N}, {n_th}) tensor with "
+                             f"1 <= m <= {nx}")
+        m, per_stage = dTh.shape[1], int(dTh.dim() == 4)
+        _check(dTh, "dTh", torch.float64, (self.B, m, N, n_th) if per_stage else (self.B, m, n_th), self.device)
+        point = self._point(point)
+        with torch.cuda.stream(self.stream):
+            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_model_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
+                                                   _ptr(point[2]), _ptr(point[3]), _ptr(dTh), per_stage, m, _ptr(dw),
+                                                   _ptr(flag), ctypes_void(self.stream.cuda_stream)))
+        return dw, flag
+
+    def sens_model_vjp(self, gw, gThk_out=None, gTh_out=None, flag_out=None, point=None, per_stage=True):
+        """Enqueue one launch of the reverse mode of :meth:`sens_model` (mpcx_sens_model_vjp_dev): gw
+        (B, m, n_w) float64 device tensor of m <= nx cotangents shaped like rows of the resident w gives
+        gThk (B, m, N, n_th), the gradient rows with respect to every stage's own model row (None with
+        per_stage=False and no gThk_out: not computed), gTh (B, m, n_th), their sum over the stages, and
+        flag (B,) int32, in the kernel's layout.  point = (P, w, lam, lamx): as :meth:`sens_vjp`; the
+        constants and bounds are the ones in force at the call.  Returns (gThk, gTh, flag) without waiting
+        for the stream."""
+        nw, nx, N, n_th = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.model_dims()
+        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
+            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
+        m = gw.shape[1]
+        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
+        point = self._point(point)
+        with torch.cuda.stream(self.stream):
+            new = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)  # noqa: E731
+            gk = gThk_out if gThk_out is not None else (new(self.B, m, N, n_th) if per_stage else None)
+            gs = new(self.B, m, n_th) if gTh_out is None else gTh_out
+            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
+        if gk is not None:
+            _check(gk, "gThk_out", torch.float64, (self.B, m, N, n_th), self.device)
+        _check(gs, "gTh_out", torch.float64, (self.B, m, n_th), self.device)
+        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
+        _lib.check(_lib.load().mpcx_sens_model_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
+                                                       _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gk),
+                                                       _ptr(gs), _ptr(flag), ctypes_void(self.stream.cuda_stream)))
+        return gk, gs, flag
+
     def set_stage_refs(self, refs):
         """Per-step stage references (tracking, param layout x0_stageref): refs is a
         (B, N*(nx+nu)) float64 device tensor copied into P[:, nx:] on the loop's stream

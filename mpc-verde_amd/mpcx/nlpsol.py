@@ -705,6 +705,174 @@ class Solver:
         np.add.at(gW, (bi[:, None, :], np.arange(m)[None, :, None], tab[:, None, :]), gk)
         return {"gWk": gk, "gW": gW, "flag": flag}
 
+    def set_par(self, par):
+        """Replace the constants ``par`` of an ODE model (mpcx_set_par; not for linear models, whose constants
+        are their tables, nor the unicycle, which has none): every later solve and sensitivity call uses them,
+        bit for bit as a solver created with these constants would."""
+        if self.ocp.model == "linear":
+            raise ValueError("set_par: a linear model's constants are its tables (set_linear_model)")
+        if self.ocp.model == "unicycle":
+            raise ValueError("set_par: the unicycle has no model constants")
+        par = tuple(float(v) for v in np.ravel(par))
+        self._h.set_par(par)
+        self.ocp = dataclasses.replace(self.ocp, par=par)
+
+    def _model_dims(self):
+        """(nx of the kernel's layout, nu, entries of the kernel's model row)."""
+        knx = self.ocp.nx if self._pad is None else self._pad.nxp
+        return knx, self.ocp.nu, self._h.model_dims()
+
+    def _model_rows(self, B, dpar, dA, dB, dc):
+        """The directions of :meth:`sens_model` as (B, m, N or 1, n_th) in the kernel's layout."""
+        if self.ocp.model == "unicycle":
+            raise ValueError("sens_model: the unicycle has no model constants")
+        lin = self.ocp.model == "linear"
+        if lin != (dpar is None) or (not lin and any(v is not None for v in (dA, dB, dc))):
+            raise ValueError("sens_model: dA / dB / dc for a linear model, dpar for the ODE models")
+        N, nx, nu = self.ocp.N, self.ocp.nx, self.ocp.nu
+        knx, _, n_th = self._model_dims()
+
+        def rows(v, tail, name):
+            v = np.asarray(v, np.float64)
+            lead = v.ndim - len(tail)
+            if lead == 1:
+                v = v[:, None, None]
+            elif lead == 2:
+                v = v[:, :, None]
+            if v.ndim != 3 + len(tail) or v.shape[0] != B or v.shape[1] < 1 or v.shape[2] not in (1, N) \
+                    or v.shape[3:] != tail:
+                raise ValueError(f"{name}: expected ({B},) + {tail}, ({B}, m) + {tail} or ({B}, m, {N}) + {tail}, "
+                                 f"got {v.shape}")
+            return v
+
+        if not lin:
+            return np.ascontiguousarray(rows(dpar, (n_th,), "dpar"))
+        if dA is None and dB is None and dc is None:
+            raise ValueError("sens_model: at least one of dA / dB / dc must be given")
+        parts = [None if v is None else rows(v, t, n) for v, t, n in
+                 ((dA, (nx, nx), "dA"), (dB, (nx, nu), "dB"), (dc, (nx,), "dc"))]
+        given = [p for p in parts if p is not None]
+        m = given[0].shape[1]
+        if any(p.shape[1] != m for p in given):
+            raise ValueError("dA / dB / dc: the same number of directions expected")
+        S = max(p.shape[2] for p in given)  # one of them per stage: the others repeated
+        d = np.zeros((B, m, S, n_th))
+        A = d[..., :knx * knx].reshape(B, m, S, knx, knx)
+        Bm = d[..., knx * knx:knx * knx + knx * nu].reshape(B, m, S, knx, nu)
+        c = d[..., knx * knx + knx * nu:]
+        if parts[0] is not None:
+            A[..., :nx, :nx] = parts[0]
+        if parts[1] is not None:
+            Bm[..., :nx, :] = parts[1]
+        if parts[2] is not None:
+            c[..., :nx] = parts[2]
+        return d
+
+    def sens_model(self, P, res, dpar=None, dA=None, dB=None, dc=None, lbw=None, ubw=None):
+        """Directional sensitivities of the solutions ``res`` to the model (mpcx_sens_model):
+        dw = (d w*/d model) d(model), no solve; every model but the unicycle, which has no constants.
+
+        dpar (the ODE models): directions of the constants the model reads (``par``: n_th entries), (B, n_th)
+        for a single one, (B, m, n_th) for m of them used at every stage, or per stage (B, m, N, n_th).
+        dA / dB / dc (linear models): directions of the stage tables in the problem's own (x, u), with
+        (nx, nx) / (nx, nu) / (nx,) in place of the row; any of them may be None (zeros); shared by the
+        stages or one per stage.  Any m (launches of at most nx columns each; a column's bits do not depend
+        on the others).  lbw / ubw: as for :meth:`sens_bounds`.
+        Returns {'dw': (B, n_w, m), 'flag': (B,)}: w(model + d) ~ w + dw (the X_0 rows are exact zeros);
+        flag 1 marks an irregular instance (NaN outputs), as :meth:`sens_x0`.  Barrier-problem
+        sensitivities (include/mpcx.h, mpcx_sens_model)."""
+        if self.ocp.formulation == "single_shooting":
+            raise ValueError("sens_model: multiple-shooting layout only")
+        if self.ocp.model == "unicycle":
+            raise ValueError("sens_model: the unicycle has no model constants")
+        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
+        d = self._model_rows(B, dpar, dA, dB, dc)
+        m, per_stage = d.shape[1], int(d.shape[2] > 1)
+        nw, knx = self._ms_nw, self.ocp.nx
+        pd = self._pad
+        if pd is not None:
+            nw, knx = pd.n_w_pad, pd.nxp
+        dw = np.empty((B, nw, m))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+
+        def call(lb, ub):
+            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
+                mc = min(knx, m - c0)
+                part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
+                dc_ = np.ascontiguousarray(d[:, c0:c0 + mc])
+                _lib.check(lib.mpcx_sens_model(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
+                                               _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(dc_),
+                                               per_stage, mc, _lib.dptr(part), _lib.iptr(fl)))
+                dw[:, :, c0:c0 + mc] = part
+                np.bitwise_or(flag, fl, out=flag)
+
+        self._with_bounds(B, lbw, ubw, per_instance, call)
+        if pd is not None:  # the model's own states and inputs only
+            dw = dw[:, pd.w_idx]
+        return {"dw": np.ascontiguousarray(dw), "flag": flag}
+
+    def sens_model_vjp(self, P, res, gw, lbw=None, ubw=None):
+        """Reverse mode of :meth:`sens_model` (mpcx_sens_model_vjp): the gradients with respect to the model
+        of a scalar loss whose gradient on the solution w is gw, from one launch:
+        <gw, sens_model(per-stage d)> = <gpark, dpar>  (linear models: <gAk, dA> + <gBk, dB> + <gck, dc>).
+
+        gw: (B, m, n_w) cotangents or (B, n_w) for a single one; any m (launches of at most nx each).
+        lbw / ubw: as for :meth:`sens_bounds`.
+        Returns 'flag' (B,) and, for the ODE models, 'gpark' (B, m, N, n_th) per stage and their sum over
+        the stages 'gpar' (B, m, n_th): the gradient with respect to the problem's ``par``.  For linear
+        models 'gAk' (B, m, N, nx, nx), 'gBk' (B, m, N, nx, nu), 'gck' (B, m, N, nx) and 'gA', 'gB', 'gc'
+        (B, m, n_tab, ...): the stages' rows summed per table through the instance's schedule.  NaN
+        outputs where flag is 1."""
+        if self.ocp.formulation == "single_shooting":
+            raise ValueError("sens_model_vjp: multiple-shooting layout only")
+        if self.ocp.model == "unicycle":
+            raise ValueError("sens_model_vjp: the unicycle has no model constants")
+        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
+        nwu = self._ms_nw
+        gw = np.asarray(gw, np.float64)
+        if gw.ndim == 2:
+            gw = gw[:, None, :]
+        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != nwu or gw.shape[1] < 1:
+            raise ValueError(f"gw: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {gw.shape}")
+        m, N = gw.shape[1], self.ocp.N
+        pd = self._pad
+        if pd is not None:
+            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
+        knx, nu, n_th = self._model_dims()
+        gk, gs = np.empty((B, m, N, n_th)), np.empty((B, m, n_th))
+        flag = np.zeros(B, np.int32)
+        lib = _lib.load()
+
+        def call(lb, ub):
+            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
+                mc = min(knx, m - c0)
+                pk, ps, fl = np.empty((B, mc, N, n_th)), np.empty((B, mc, n_th)), np.empty(B, np.int32)
+                gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
+                _lib.check(lib.mpcx_sens_model_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
+                                                   _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(gwc), mc,
+                                                   _lib.dptr(pk), _lib.dptr(ps), _lib.iptr(fl)))
+                gk[:, c0:c0 + mc], gs[:, c0:c0 + mc] = pk, ps
+                np.bitwise_or(flag, fl, out=flag)
+
+        self._with_bounds(B, lbw, ubw, per_instance, call)
+        if self.ocp.model != "linear":
+            return {"gpar": gs, "gpark": gk, "flag": flag}
+        nx = self.ocp.nx
+        gAk = np.ascontiguousarray(gk[..., :knx * knx].reshape(B, m, N, knx, knx)[..., :nx, :nx])
+        gBk = np.ascontiguousarray(gk[..., knx * knx:knx * knx + knx * nu].reshape(B, m, N, knx, nu)[..., :nx, :])
+        gck = np.ascontiguousarray(gk[..., knx * knx + knx * nu:][..., :nx])
+        tab = np.asarray(self.ocp.tab)
+        tab = tab[None, :] if tab.ndim == 1 else tab
+        tab = np.broadcast_to(tab, (B, N)) if tab.shape[0] == 1 else tab[:B]
+        bi = np.broadcast_to(np.arange(B)[:, None], (B, N))
+        out = {"gAk": gAk, "gBk": gBk, "gck": gck, "flag": flag}
+        for name, v in (("gA", gAk), ("gB", gBk), ("gc", gck)):  # summed over the schedule, as gW is
+            acc = np.zeros((B, m, self.ocp.n_tab) + v.shape[3:])
+            np.add.at(acc, (bi[:, None, :], np.arange(m)[None, :, None], tab[:, None, :]), v)
+            out[name] = acc
+        return out
+
     def rk4_sens(self, w, P):
         """Per-interval defects, costs and Jacobians at w (B, n_w) -- the sweep kernel."""
         if self.ocp.model != "unicycle":
