@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -884,349 +885,6 @@ int mpcx_shift_dev(mpcx_handle* h, int32_t B, double* d_P, const double* d_w, do
   return 0;
 }
 
-// what both sensitivity entry points refuse before anything is launched
-static int check_sens_args(const mpcx_handle* h, int B, const void* P, const void* w, const void* lam_g,
-                           const void* lam_x, const void* dw, const void* K0) {
-  if (!h) return fail(MPCX_EINVAL, "null handle");
-  if (B <= 0) return fail(MPCX_EINVAL, "sens_x0: B must be >= 1");
-  if (!P || !w || !lam_g || !lam_x) return fail(MPCX_EINVAL, "sens_x0: P, w, lam_g and lam_x are required");
-  if (!dw && !K0) return fail(MPCX_EINVAL, "sens_x0: at least one of dw_dx0 / K0 must be given");
-  if (h->spec.N >= 64)
-    return fail(MPCX_EINVAL, "sens_x0: horizons N >= 64 (lane groups wider than a wavefront) are not supported");
-  if (int r = check_model_ready(h, B)) return r;
-  return 0;
-}
-
-int mpcx_sens_x0_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
-                     const double* d_lam_x, double* d_dw_dx0, double* d_K0, int32_t* d_flag, void* stream) {
-  if (int r = check_sens_args(h, B, d_P, d_w, d_lam_g, d_lam_x, d_dw_dx0, d_K0)) return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens(a, d_w, d_lam_g, d_lam_x, d_dw_dx0, d_K0, d_flag, (hipStream_t)stream));
-  return 0;
-}
-
-int mpcx_sens_x0(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
-                 const double* lam_x, const double* lbw, const double* ubw, double* dw_dx0, double* K0,
-                 int32_t* flag) {
-  if (int r = check_sens_args(h, B, P, w, lam_g, lam_x, dw_dx0, K0)) return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
-  const int nx = h->spec.nx, nu = h->spec.nu;
-  const size_t n_dw = (size_t)B * h->nw * nx, n_k0 = (size_t)B * nu * nx;
-  if (n_dw + n_k0 > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_dw + n_k0) * sizeof(double)));
-    h->cap_sens = n_dw + n_k0;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  double *d_dw = h->d_sens, *d_k0 = h->d_sens + n_dw;
-  HIPCHK(ops->sens(a, h->d_w, h->d_lam, h->d_lamx, d_dw, d_k0, h->d_status, s));
-  if (dw_dx0) HIPCHK(hipMemcpyAsync(dw_dx0, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (K0) HIPCHK(hipMemcpyAsync(K0, d_k0, n_k0 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-
-// what both parameter-sensitivity entry points refuse before anything is launched
-static int check_sens_p_args(const mpcx_handle* h, int B, const void* P, const void* w, const void* lam_g,
-                             const void* lam_x, const void* dP, int m, const void* dw) {
-  if (!h) return fail(MPCX_EINVAL, "null handle");
-  if (B <= 0) return fail(MPCX_EINVAL, "sens_p: B must be >= 1");
-  if (!P || !w || !lam_g || !lam_x || !dP || !dw)
-    return fail(MPCX_EINVAL, "sens_p: P, w, lam_g, lam_x, dP and dw are required");
-  if (m < 1 || m > h->spec.nx) return fail(MPCX_EINVAL, "sens_p: m must be between 1 and nx directions per call");
-  if (h->spec.N >= 64)
-    return fail(MPCX_EINVAL, "sens_p: horizons N >= 64 (lane groups wider than a wavefront) are not supported");
-  if (h->spec.model == MPCX_MODEL_PATH_BICYCLE)
-    return fail(MPCX_EINVAL, "sens_p: the path-frame bicycle's stage rows enter its dynamics; not supported");
-  if (int r = check_model_ready(h, B)) return r;
-  return 0;
-}
-
-int mpcx_sens_p_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
-                    const double* d_lam_x, const double* d_dP, int32_t m, double* d_dw, int32_t* d_flag,
-                    void* stream) {
-  if (int r = check_sens_p_args(h, B, d_P, d_w, d_lam_g, d_lam_x, d_dP, m, d_dw)) return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_p(a, d_w, d_lam_g, d_lam_x, d_dP, m, d_dw, d_flag, (hipStream_t)stream));
-  return 0;
-}
-
-int mpcx_sens_p(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
-                const double* lam_x, const double* lbw, const double* ubw, const double* dP, int32_t m, double* dw,
-                int32_t* flag) {
-  if (int r = check_sens_p_args(h, B, P, w, lam_g, lam_x, dP, m, dw)) return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
-  const size_t n_dw = (size_t)B * h->nw * m, n_dp = (size_t)B * m * h->np;
-  if (n_dw + n_dp > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_dw + n_dp) * sizeof(double)));
-    h->cap_sens = n_dw + n_dp;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_dw = h->d_sens, *d_dp = h->d_sens + n_dw;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_dp, dP, n_dp * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_p(a, h->d_w, h->d_lam, h->d_lamx, d_dp, m, d_dw, h->d_status, s));
-  HIPCHK(hipMemcpyAsync(dw, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-
-// what both adjoint-sensitivity entry points refuse before anything is launched
-static int check_sens_vjp_args(const mpcx_handle* h, int B, const void* P, const void* w, const void* lam_g,
-                               const void* lam_x, const void* gw, int m, const void* gP) {
-  if (!h) return fail(MPCX_EINVAL, "null handle");
-  if (B <= 0) return fail(MPCX_EINVAL, "sens_vjp: B must be >= 1");
-  if (!P || !w || !lam_g || !lam_x || !gw || !gP)
-    return fail(MPCX_EINVAL, "sens_vjp: P, w, lam_g, lam_x, gw and gP are required");
-  if (m < 1 || m > h->spec.nx) return fail(MPCX_EINVAL, "sens_vjp: m must be between 1 and nx cotangents per call");
-  if (h->spec.N >= 64)
-    return fail(MPCX_EINVAL, "sens_vjp: horizons N >= 64 (lane groups wider than a wavefront) are not supported");
-  if (h->spec.model == MPCX_MODEL_PATH_BICYCLE)
-    return fail(MPCX_EINVAL, "sens_vjp: the path-frame bicycle's stage rows enter its dynamics; not supported");
-  if (int r = check_model_ready(h, B)) return r;
-  return 0;
-}
-
-int mpcx_sens_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
-                      const double* d_lam_x, const double* d_gw, int32_t m, double* d_gP, int32_t* d_flag,
-                      void* stream) {
-  if (int r = check_sens_vjp_args(h, B, d_P, d_w, d_lam_g, d_lam_x, d_gw, m, d_gP)) return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gP, d_flag, (hipStream_t)stream));
-  return 0;
-}
-
-int mpcx_sens_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
-                  const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m, double* gP,
-                  int32_t* flag) {
-  if (int r = check_sens_vjp_args(h, B, P, w, lam_g, lam_x, gw, m, gP)) return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
-  const size_t n_gp = (size_t)B * m * h->np, n_gw = (size_t)B * m * h->nw;
-  if (n_gp + n_gw > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_gp + n_gw) * sizeof(double)));
-    h->cap_sens = n_gp + n_gw;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_gp = h->d_sens, *d_gw = h->d_sens + n_gp;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_gw, gw, n_gw * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_vjp(a, h->d_w, h->d_lam, h->d_lamx, d_gw, m, d_gp, h->d_status, s));
-  HIPCHK(hipMemcpyAsync(gP, d_gp, n_gp * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-
-// what the four bound-sensitivity entry points refuse before anything is launched (every model is
-// accepted: the right-hand sides come from Sigma, no reference hook of the model)
-static int check_sens_bounds_args(const mpcx_handle* h, int B, const char* who, bool ptrs, int m) {
-  auto say = [&](const char* what) { return fail(MPCX_EINVAL, std::string(who) + ": " + what); };
-  if (!h) return fail(MPCX_EINVAL, "null handle");
-  if (B <= 0) return say("B must be >= 1");
-  if (!ptrs) return say("P, w, lam_g, lam_x, the directions or cotangents and the outputs are required");
-  if (m < 1 || m > h->spec.nx) return say("m must be between 1 and nx columns per call");
-  if (h->spec.N >= 64) return say("horizons N >= 64 (lane groups wider than a wavefront) are not supported");
-  if (int r = check_model_ready(h, B)) return r;
-  return 0;
-}
-
-int mpcx_sens_bounds_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
-                         const double* d_lam_x, const double* d_dlbw, const double* d_dubw, int32_t m, double* d_dw,
-                         int32_t* d_flag, void* stream) {
-  if (int r = check_sens_bounds_args(h, B, "sens_bounds", d_P && d_w && d_lam_g && d_lam_x && d_dlbw && d_dubw && d_dw, m))
-    return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_bnd(a, d_w, d_lam_g, d_lam_x, d_dlbw, d_dubw, m, d_dw, d_flag, (hipStream_t)stream));
-  return 0;
-}
-
-int mpcx_sens_bounds(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
-                     const double* lam_x, const double* lbw, const double* ubw, const double* dlbw,
-                     const double* dubw, int32_t m, double* dw, int32_t* flag) {
-  if (int r = check_sens_bounds_args(h, B, "sens_bounds", P && w && lam_g && lam_x && dlbw && dubw && dw, m)) return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
-  const size_t n_dw = (size_t)B * h->nw * m, n_d = (size_t)B * m * h->nw;
-  if (n_dw + 2 * n_d > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_dw + 2 * n_d) * sizeof(double)));
-    h->cap_sens = n_dw + 2 * n_d;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_dw = h->d_sens, *d_dl = h->d_sens + n_dw, *d_du = d_dl + n_d;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_dl, dlbw, n_d * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_du, dubw, n_d * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_bnd(a, h->d_w, h->d_lam, h->d_lamx, d_dl, d_du, m, d_dw, h->d_status, s));
-  HIPCHK(hipMemcpyAsync(dw, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-
-int mpcx_sens_bounds_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
-                             const double* d_lam_x, const double* d_gw, int32_t m, double* d_glbw, double* d_gubw,
-                             int32_t* d_flag, void* stream) {
-  if (int r = check_sens_bounds_args(h, B, "sens_bounds_vjp", d_P && d_w && d_lam_g && d_lam_x && d_gw && d_glbw && d_gubw,
-                                     m))
-    return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_bnd_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_glbw, d_gubw, d_flag, (hipStream_t)stream));
-  return 0;
-}
-
-int mpcx_sens_bounds_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
-                         const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
-                         double* glbw, double* gubw, int32_t* flag) {
-  if (int r = check_sens_bounds_args(h, B, "sens_bounds_vjp", P && w && lam_g && lam_x && gw && glbw && gubw, m)) return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
-  const size_t n_g = (size_t)B * m * h->nw;
-  if (3 * n_g > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, 3 * n_g * sizeof(double)));
-    h->cap_sens = 3 * n_g;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_gl = h->d_sens, *d_gu = d_gl + n_g, *d_gw = d_gu + n_g;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_gw, gw, n_g * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_bnd_vjp(a, h->d_w, h->d_lam, h->d_lamx, d_gw, m, d_gl, d_gu, h->d_status, s));
-  HIPCHK(hipMemcpyAsync(glbw, d_gl, n_g * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(gubw, d_gu, n_g * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-
 // the unit of the handle's model (nx, nu, N, the spec's state bounds): its weight row and launches
 static const mpcx::ModelOps* handle_ops(const mpcx_handle* h) {
   mpcx::SolveArgs a{};
@@ -1260,139 +918,6 @@ int mpcx_set_weights(mpcx_handle* h, const double* Q, const double* R) {
   return 0;
 }
 
-// what the four weight-sensitivity entry points refuse before anything is launched
-static int check_sens_weights_args(const mpcx_handle* h, int B, const char* who, bool ptrs, int m) {
-  auto say = [&](const char* what) { return fail(MPCX_EINVAL, std::string(who) + ": " + what); };
-  if (!h) return fail(MPCX_EINVAL, "null handle");
-  if (B <= 0) return say("B must be >= 1");
-  if (!ptrs) return say("P, w, lam_g, lam_x, the directions or cotangents and an output are required");
-  if (m < 1 || m > h->spec.nx) return say("m must be between 1 and nx columns per call");
-  if (h->spec.N >= 64) return say("horizons N >= 64 (lane groups wider than a wavefront) are not supported");
-  if (int r = check_model_ready(h, B)) return r;
-  return 0;
-}
-
-int mpcx_sens_weights_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
-                          const double* d_lam_x, const double* d_dW, int32_t per_stage, int32_t m, double* d_dw,
-                          int32_t* d_flag, void* stream) {
-  if (int r = check_sens_weights_args(h, B, "sens_weights", d_P && d_w && d_lam_g && d_lam_x && d_dW && d_dw, m)) return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_wt(a, d_w, d_lam_g, d_lam_x, d_dW, per_stage, m, d_dw, d_flag, (hipStream_t)stream));
-  return 0;
-}
-
-int mpcx_sens_weights(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
-                      const double* lam_x, const double* lbw, const double* ubw, const double* dW, int32_t per_stage,
-                      int32_t m, double* dw, int32_t* flag) {
-  if (int r = check_sens_weights_args(h, B, "sens_weights", P && w && lam_g && lam_x && dW && dw, m)) return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
-  const mpcx::ModelOps* hops = handle_ops(h);
-  if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
-  const size_t n_dw = (size_t)B * h->nw * m, n_d = (size_t)B * m * (per_stage ? h->spec.N : 1) * hops->n_wt;
-  if (n_dw + n_d > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_dw + n_d) * sizeof(double)));
-    h->cap_sens = n_dw + n_d;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_dw = h->d_sens, *d_d = h->d_sens + n_dw;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_d, dW, n_d * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_wt(a, h->d_w, h->d_lam, h->d_lamx, d_d, per_stage, m, d_dw, h->d_status, s));
-  HIPCHK(hipMemcpyAsync(dw, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-
-int mpcx_sens_weights_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
-                              const double* d_lam_x, const double* d_gw, int32_t m, double* d_gWk, double* d_gW,
-                              int32_t* d_flag, void* stream) {
-  if (int r = check_sens_weights_args(h, B, "sens_weights_vjp",
-                                      d_P && d_w && d_lam_g && d_lam_x && d_gw && (d_gWk || d_gW), m))
-    return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_wt_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gWk, d_gW, d_flag, (hipStream_t)stream));
-  return 0;
-}
-
-int mpcx_sens_weights_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
-                          const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
-                          double* gWk, double* gW, int32_t* flag) {
-  if (int r = check_sens_weights_args(h, B, "sens_weights_vjp", P && w && lam_g && lam_x && gw && (gWk || gW), m))
-    return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
-  const mpcx::ModelOps* hops = handle_ops(h);
-  if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
-  const size_t n_g = (size_t)B * m * h->nw, n_s = (size_t)B * m * hops->n_wt, n_k = n_s * h->spec.N;
-  if (n_g + n_s + n_k > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_g + n_s + n_k) * sizeof(double)));
-    h->cap_sens = n_g + n_s + n_k;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_gw = h->d_sens, *d_gs = d_gw + n_g, *d_gk = d_gs + n_s;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_gw, gw, n_g * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_wt_vjp(a, h->d_w, h->d_lam, h->d_lamx, d_gw, m, gWk ? d_gk : nullptr, gW ? d_gs : nullptr,
-                          h->d_status, s));
-  if (gWk) HIPCHK(hipMemcpyAsync(gWk, d_gk, n_k * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (gW) HIPCHK(hipMemcpyAsync(gW, d_gs, n_s * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-
 int mpcx_model_dims(const mpcx_handle* h, int32_t* n_th) {
   if (!h) return fail(MPCX_EINVAL, "null handle");
   const mpcx::ModelOps* ops = handle_ops(h);
@@ -1417,138 +942,355 @@ int mpcx_set_par(mpcx_handle* h, const double* par) {
   return 0;
 }
 
-// what the four model-sensitivity entry points refuse before anything is launched
-static int check_sens_model_args(const mpcx_handle* h, int B, const char* who, bool ptrs, int m) {
-  auto say = [&](const char* what) { return fail(MPCX_EINVAL, std::string(who) + ": " + what); };
+}  // extern "C"
+
+// ---- sensitivities of the solution (sens.h) ------------------------------------------------------
+// Nine calls, each with a device-pointer and a host-pointer entry point.  All take the point (P, w,
+// lam_g, lam_x) and differ in their further inputs, their outputs and one launch of the model's unit;
+// check_sens_args, sens_dev and sens_host below are what they share.
+namespace {
+
+// what the model must have for a call (refused with the call's own wording when it has not)
+enum SensNeeds { SENS_ANY_MODEL, SENS_REF_TANGENT, SENS_CONSTANTS };
+
+// a call as its argument check sees it; both of its entry points use the same one
+struct SensCall {
+  const char* who;       // the prefix of its refusals
+  const char* required;  // the refusal of a missing pointer
+  const char* m_unit;    // what its m columns are called, or null: the call has no m
+  SensNeeds needs;
+};
+#define SENS_ALL_PTRS "P, w, lam_g, lam_x, the directions or cotangents and the outputs are required"
+#define SENS_ONE_PTR "P, w, lam_g, lam_x, the directions or cotangents and an output are required"
+const SensCall kSensX0{"sens_x0", "P, w, lam_g and lam_x are required", nullptr, SENS_ANY_MODEL};
+const SensCall kSensP{"sens_p", "P, w, lam_g, lam_x, dP and dw are required", "directions", SENS_REF_TANGENT};
+const SensCall kSensVjp{"sens_vjp", "P, w, lam_g, lam_x, gw and gP are required", "cotangents", SENS_REF_TANGENT};
+// (the bound sensitivities take every model: the right-hand sides come from Sigma, no reference hook)
+const SensCall kSensBounds{"sens_bounds", SENS_ALL_PTRS, "columns", SENS_ANY_MODEL};
+const SensCall kSensBoundsVjp{"sens_bounds_vjp", SENS_ALL_PTRS, "columns", SENS_ANY_MODEL};
+const SensCall kSensWeights{"sens_weights", SENS_ONE_PTR, "columns", SENS_ANY_MODEL};
+const SensCall kSensWeightsVjp{"sens_weights_vjp", SENS_ONE_PTR, "columns", SENS_ANY_MODEL};
+const SensCall kSensModel{"sens_model", SENS_ONE_PTR, "columns", SENS_CONSTANTS};
+const SensCall kSensModelVjp{"sens_model_vjp", SENS_ONE_PTR, "columns", SENS_CONSTANTS};
+#undef SENS_ALL_PTRS
+#undef SENS_ONE_PTR
+
+// What the two entry points of a sensitivity call refuse before anything is launched, in this order:
+// null handle, B, a missing pointer (`given` = all required ones are there), sens_x0 without an output,
+// a model without constants, m, the horizon, a model without a reference tangent, a linear model
+// without tables.
+int check_sens_args(const mpcx_handle* h, int B, const SensCall& c, bool given, int m = 0, bool an_output = true) {
+  auto say = [&](const std::string& what) { return fail(MPCX_EINVAL, std::string(c.who) + ": " + what); };
   if (!h) return fail(MPCX_EINVAL, "null handle");
   if (B <= 0) return say("B must be >= 1");
-  if (!ptrs) return say("P, w, lam_g, lam_x, the directions or cotangents and an output are required");
-  if (h->spec.model == MPCX_MODEL_UNICYCLE) return say("the unicycle has no model constants (n_th = 0)");
-  if (m < 1 || m > h->spec.nx) return say("m must be between 1 and nx columns per call");
+  if (!given) return say(c.required);
+  if (!an_output) return say("at least one of dw_dx0 / K0 must be given");
+  if (c.needs == SENS_CONSTANTS && h->spec.model == MPCX_MODEL_UNICYCLE)
+    return say("the unicycle has no model constants (n_th = 0)");
+  if (c.m_unit && (m < 1 || m > h->spec.nx))
+    return say(std::string("m must be between 1 and nx ") + c.m_unit + " per call");
   if (h->spec.N >= 64) return say("horizons N >= 64 (lane groups wider than a wavefront) are not supported");
-  if (int r = check_model_ready(h, B)) return r;
+  if (c.needs == SENS_REF_TANGENT && h->spec.model == MPCX_MODEL_PATH_BICYCLE)
+    return say("the path-frame bicycle's stage rows enter its dynamics; not supported");
+  return check_model_ready(h, B);
+}
+
+// A device-pointer entry point after its argument check: launch(ops, a) makes the one call of the
+// model's unit, on the caller's stream; nothing is staged and nothing waits.
+template <class Launch>
+int sens_dev(mpcx_handle* h, int B, const double* d_P, Launch&& launch) {
+  if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(launch(ops, a));
   return 0;
+}
+
+// the staged point and the carved device arrays a host-pointer call hands to its launch
+struct SensStage {
+  const double *w, *lam_g, *lam_x;  // (P is SolveArgs::P)
+  const double* in[2];              // the call's further inputs, in the order given
+  double* out[2];                   // its outputs, in the order given (carved whether asked for or not)
+  int32_t* flag;
+};
+struct HostIn {
+  const double* p;
+  size_t n;
+};
+struct HostOut {
+  double* p;  // null: not asked for (not copied back)
+  size_t n;
+};
+
+// A host-pointer entry point after its argument check: the point, the call's own bounds (either may
+// be null) and the further inputs `in` are staged on the handle's stream, launch(ops, a, stage, stream)
+// makes the one call of the model's unit, the outputs asked for and the flag (optional) are copied
+// back, and the call waits for them.
+template <class Launch>
+int sens_host(mpcx_handle* h, int B, const double* P, const double* w, const double* lam_g, const double* lam_x,
+              const double* lbw, const double* ubw, std::initializer_list<HostIn> in,
+              std::initializer_list<HostOut> out, int32_t* flag, Launch&& launch) {
+  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
+  if (!lbw && !ubw)
+    if (int r = check_bound_rows(h, B)) return r;
+  DEVICE_SCOPE(h->spec.device);
+  if (int r = ensure(h, B)) return r;
+  hipStream_t s = h->stream;
+  size_t need = 0;
+  for (const HostOut& o : out) need += o.n;
+  for (const HostIn& i : in) need += i.n;
+  if (need > h->cap_sens) {  // grown on demand, never shrunk
+    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
+    dev_free(h->d_sens);
+    h->cap_sens = 0;
+    HIPCHK(hipMalloc(&h->d_sens, need * sizeof(double)));
+    h->cap_sens = need;
+  }
+  int call_xbnd = 0;
+  if (lbw || ubw)
+    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
+  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
+  SensStage st{h->d_w, h->d_lam, h->d_lamx, {}, {}, h->d_status};
+  double* d = h->d_sens;
+  int k = 0;
+  for (const HostOut& o : out) {
+    st.out[k++] = d;
+    d += o.n;
+  }
+  k = 0;
+  for (const HostIn& i : in) {
+    HIPCHK(hipMemcpyAsync(d, i.p, i.n * sizeof(double), hipMemcpyHostToDevice, s));
+    st.in[k++] = d;
+    d += i.n;
+  }
+  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
+  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
+    a.lbw = h->d_lbw_call;
+    a.ubw = h->d_ubw_call;
+    a.bnd_row = 0;
+    a.xbnd = call_xbnd;
+  }
+  const mpcx::ModelOps* ops = mpcx::model_ops(a);
+  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
+  HIPCHK(launch(ops, a, st, s));
+  k = 0;
+  for (const HostOut& o : out) {
+    if (o.p) HIPCHK(hipMemcpyAsync(o.p, st.out[k], o.n * sizeof(double), hipMemcpyDeviceToHost, s));
+    ++k;
+  }
+  if (flag) HIPCHK(hipMemcpyAsync(flag, st.flag, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+// entries of a batch's rows of weights (`n_row` = ModelOps::n_wt) or model constants (n_th): one row
+// per stage or one for all stages
+size_t stage_rows(const mpcx_handle* h, int B, int m, int per_stage, int n_row) {
+  return (size_t)B * m * (per_stage ? h->spec.N : 1) * n_row;
+}
+}  // namespace
+
+extern "C" {
+
+int mpcx_sens_x0_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                     const double* d_lam_x, double* d_dw_dx0, double* d_K0, int32_t* d_flag, void* stream) {
+  if (int r = check_sens_args(h, B, kSensX0, d_P && d_w && d_lam_g && d_lam_x, 0, d_dw_dx0 || d_K0)) return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens(a, d_w, d_lam_g, d_lam_x, d_dw_dx0, d_K0, d_flag, (hipStream_t)stream);
+  });
+}
+
+int mpcx_sens_x0(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                 const double* lam_x, const double* lbw, const double* ubw, double* dw_dx0, double* K0,
+                 int32_t* flag) {
+  if (int r = check_sens_args(h, B, kSensX0, P && w && lam_g && lam_x, 0, dw_dx0 || K0)) return r;
+  const size_t n_dw = (size_t)B * h->nw * h->spec.nx, n_k0 = (size_t)B * h->spec.nu * h->spec.nx;
+  // (both outputs are always computed; only those asked for are copied back)
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {}, {{dw_dx0, n_dw}, {K0, n_k0}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens(a, st.w, st.lam_g, st.lam_x, st.out[0], st.out[1], st.flag, s);
+                   });
+}
+
+int mpcx_sens_p_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                    const double* d_lam_x, const double* d_dP, int32_t m, double* d_dw, int32_t* d_flag,
+                    void* stream) {
+  if (int r = check_sens_args(h, B, kSensP, d_P && d_w && d_lam_g && d_lam_x && d_dP && d_dw, m)) return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_p(a, d_w, d_lam_g, d_lam_x, d_dP, m, d_dw, d_flag, (hipStream_t)stream);
+  });
+}
+
+int mpcx_sens_p(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                const double* lam_x, const double* lbw, const double* ubw, const double* dP, int32_t m, double* dw,
+                int32_t* flag) {
+  if (int r = check_sens_args(h, B, kSensP, P && w && lam_g && lam_x && dP && dw, m)) return r;
+  const size_t n_dw = (size_t)B * h->nw * m, n_dp = (size_t)B * m * h->np;
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{dP, n_dp}}, {{dw, n_dw}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_p(a, st.w, st.lam_g, st.lam_x, st.in[0], m, st.out[0], st.flag, s);
+                   });
+}
+
+int mpcx_sens_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                      const double* d_lam_x, const double* d_gw, int32_t m, double* d_gP, int32_t* d_flag,
+                      void* stream) {
+  if (int r = check_sens_args(h, B, kSensVjp, d_P && d_w && d_lam_g && d_lam_x && d_gw && d_gP, m)) return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gP, d_flag, (hipStream_t)stream);
+  });
+}
+
+int mpcx_sens_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                  const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m, double* gP,
+                  int32_t* flag) {
+  if (int r = check_sens_args(h, B, kSensVjp, P && w && lam_g && lam_x && gw && gP, m)) return r;
+  const size_t n_gp = (size_t)B * m * h->np, n_gw = (size_t)B * m * h->nw;
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{gw, n_gw}}, {{gP, n_gp}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_vjp(a, st.w, st.lam_g, st.lam_x, st.in[0], m, st.out[0], st.flag, s);
+                   });
+}
+
+int mpcx_sens_bounds_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                         const double* d_lam_x, const double* d_dlbw, const double* d_dubw, int32_t m, double* d_dw,
+                         int32_t* d_flag, void* stream) {
+  if (int r = check_sens_args(h, B, kSensBounds, d_P && d_w && d_lam_g && d_lam_x && d_dlbw && d_dubw && d_dw, m))
+    return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_bnd(a, d_w, d_lam_g, d_lam_x, d_dlbw, d_dubw, m, d_dw, d_flag, (hipStream_t)stream);
+  });
+}
+
+int mpcx_sens_bounds(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                     const double* lam_x, const double* lbw, const double* ubw, const double* dlbw,
+                     const double* dubw, int32_t m, double* dw, int32_t* flag) {
+  if (int r = check_sens_args(h, B, kSensBounds, P && w && lam_g && lam_x && dlbw && dubw && dw, m)) return r;
+  const size_t n = (size_t)B * m * h->nw;
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{dlbw, n}, {dubw, n}}, {{dw, n}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_bnd(a, st.w, st.lam_g, st.lam_x, st.in[0], st.in[1], m, st.out[0], st.flag, s);
+                   });
+}
+
+int mpcx_sens_bounds_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                             const double* d_lam_x, const double* d_gw, int32_t m, double* d_glbw, double* d_gubw,
+                             int32_t* d_flag, void* stream) {
+  if (int r = check_sens_args(h, B, kSensBoundsVjp, d_P && d_w && d_lam_g && d_lam_x && d_gw && d_glbw && d_gubw, m))
+    return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_bnd_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_glbw, d_gubw, d_flag, (hipStream_t)stream);
+  });
+}
+
+int mpcx_sens_bounds_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                         const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
+                         double* glbw, double* gubw, int32_t* flag) {
+  if (int r = check_sens_args(h, B, kSensBoundsVjp, P && w && lam_g && lam_x && gw && glbw && gubw, m)) return r;
+  const size_t n = (size_t)B * m * h->nw;
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{gw, n}}, {{glbw, n}, {gubw, n}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_bnd_vjp(a, st.w, st.lam_g, st.lam_x, st.in[0], m, st.out[0], st.out[1], st.flag,
+                                              s);
+                   });
+}
+
+int mpcx_sens_weights_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                          const double* d_lam_x, const double* d_dW, int32_t per_stage, int32_t m, double* d_dw,
+                          int32_t* d_flag, void* stream) {
+  if (int r = check_sens_args(h, B, kSensWeights, d_P && d_w && d_lam_g && d_lam_x && d_dW && d_dw, m)) return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_wt(a, d_w, d_lam_g, d_lam_x, d_dW, per_stage, m, d_dw, d_flag, (hipStream_t)stream);
+  });
+}
+
+int mpcx_sens_weights(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                      const double* lam_x, const double* lbw, const double* ubw, const double* dW, int32_t per_stage,
+                      int32_t m, double* dw, int32_t* flag) {
+  if (int r = check_sens_args(h, B, kSensWeights, P && w && lam_g && lam_x && dW && dw, m)) return r;
+  const mpcx::ModelOps* hops = handle_ops(h);
+  if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
+  const size_t n_dw = (size_t)B * h->nw * m, n_d = stage_rows(h, B, m, per_stage, hops->n_wt);
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{dW, n_d}}, {{dw, n_dw}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_wt(a, st.w, st.lam_g, st.lam_x, st.in[0], per_stage, m, st.out[0], st.flag, s);
+                   });
+}
+
+int mpcx_sens_weights_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
+                              const double* d_lam_x, const double* d_gw, int32_t m, double* d_gWk, double* d_gW,
+                              int32_t* d_flag, void* stream) {
+  if (int r = check_sens_args(h, B, kSensWeightsVjp, d_P && d_w && d_lam_g && d_lam_x && d_gw && (d_gWk || d_gW), m))
+    return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_wt_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gWk, d_gW, d_flag, (hipStream_t)stream);
+  });
+}
+
+int mpcx_sens_weights_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
+                          const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
+                          double* gWk, double* gW, int32_t* flag) {
+  if (int r = check_sens_args(h, B, kSensWeightsVjp, P && w && lam_g && lam_x && gw && (gWk || gW), m)) return r;
+  const mpcx::ModelOps* hops = handle_ops(h);
+  if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
+  const size_t n_g = (size_t)B * m * h->nw, n_s = stage_rows(h, B, m, 0, hops->n_wt), n_k = n_s * h->spec.N;
+  // (an output not asked for is not computed: its device pointer is null)
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{gw, n_g}}, {{gWk, n_k}, {gW, n_s}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_wt_vjp(a, st.w, st.lam_g, st.lam_x, st.in[0], m, gWk ? st.out[0] : nullptr,
+                                             gW ? st.out[1] : nullptr, st.flag, s);
+                   });
 }
 
 int mpcx_sens_model_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
                         const double* d_lam_x, const double* d_dTh, int32_t per_stage, int32_t m, double* d_dw,
                         int32_t* d_flag, void* stream) {
-  if (int r = check_sens_model_args(h, B, "sens_model", d_P && d_w && d_lam_g && d_lam_x && d_dTh && d_dw, m)) return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_mdl(a, d_w, d_lam_g, d_lam_x, d_dTh, per_stage, m, d_dw, d_flag, (hipStream_t)stream));
-  return 0;
+  if (int r = check_sens_args(h, B, kSensModel, d_P && d_w && d_lam_g && d_lam_x && d_dTh && d_dw, m)) return r;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_mdl(a, d_w, d_lam_g, d_lam_x, d_dTh, per_stage, m, d_dw, d_flag, (hipStream_t)stream);
+  });
 }
 
 int mpcx_sens_model(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
                     const double* lam_x, const double* lbw, const double* ubw, const double* dTh, int32_t per_stage,
                     int32_t m, double* dw, int32_t* flag) {
-  if (int r = check_sens_model_args(h, B, "sens_model", P && w && lam_g && lam_x && dTh && dw, m)) return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
+  if (int r = check_sens_args(h, B, kSensModel, P && w && lam_g && lam_x && dTh && dw, m)) return r;
   const mpcx::ModelOps* hops = handle_ops(h);
   if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
-  const size_t n_dw = (size_t)B * h->nw * m, n_d = (size_t)B * m * (per_stage ? h->spec.N : 1) * hops->n_th;
-  if (n_dw + n_d > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_dw + n_d) * sizeof(double)));
-    h->cap_sens = n_dw + n_d;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_dw = h->d_sens, *d_d = h->d_sens + n_dw;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_d, dTh, n_d * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_mdl(a, h->d_w, h->d_lam, h->d_lamx, d_d, per_stage, m, d_dw, h->d_status, s));
-  HIPCHK(hipMemcpyAsync(dw, d_dw, n_dw * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  const size_t n_dw = (size_t)B * h->nw * m, n_d = stage_rows(h, B, m, per_stage, hops->n_th);
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{dTh, n_d}}, {{dw, n_dw}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_mdl(a, st.w, st.lam_g, st.lam_x, st.in[0], per_stage, m, st.out[0], st.flag, s);
+                   });
 }
 
 int mpcx_sens_model_vjp_dev(mpcx_handle* h, int32_t B, const double* d_P, const double* d_w, const double* d_lam_g,
                             const double* d_lam_x, const double* d_gw, int32_t m, double* d_gThk, double* d_gTh,
                             int32_t* d_flag, void* stream) {
-  if (int r = check_sens_model_args(h, B, "sens_model_vjp",
-                                    d_P && d_w && d_lam_g && d_lam_x && d_gw && (d_gThk || d_gTh), m))
+  if (int r = check_sens_args(h, B, kSensModelVjp, d_P && d_w && d_lam_g && d_lam_x && d_gw && (d_gThk || d_gTh), m))
     return r;
-  if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  const mpcx::SolveArgs a = make_args(h, B, {.P = d_P});
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_mdl_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gThk, d_gTh, d_flag, (hipStream_t)stream));
-  return 0;
+  return sens_dev(h, B, d_P, [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a) {
+    return ops->sens_mdl_vjp(a, d_w, d_lam_g, d_lam_x, d_gw, m, d_gThk, d_gTh, d_flag, (hipStream_t)stream);
+  });
 }
 
 int mpcx_sens_model_vjp(mpcx_handle* h, int32_t B, const double* P, const double* w, const double* lam_g,
                         const double* lam_x, const double* lbw, const double* ubw, const double* gw, int32_t m,
                         double* gThk, double* gTh, int32_t* flag) {
-  if (int r = check_sens_model_args(h, B, "sens_model_vjp", P && w && lam_g && lam_x && gw && (gThk || gTh), m))
-    return r;
-  if (int r = check_bounds_vec(h, lbw, ubw)) return r;
-  if (!lbw && !ubw)
-    if (int r = check_bound_rows(h, B)) return r;
-  DEVICE_SCOPE(h->spec.device);
-  if (int r = ensure(h, B)) return r;
-  hipStream_t s = h->stream;
+  if (int r = check_sens_args(h, B, kSensModelVjp, P && w && lam_g && lam_x && gw && (gThk || gTh), m)) return r;
   const mpcx::ModelOps* hops = handle_ops(h);
   if (!hops) return fail(MPCX_EINVAL, "no kernel for this model");
-  const size_t n_g = (size_t)B * m * h->nw, n_s = (size_t)B * m * hops->n_th, n_k = n_s * h->spec.N;
-  if (n_g + n_s + n_k > h->cap_sens) {
-    HIPCHK(hipStreamSynchronize(s));  // (host-pointer calls are synchronous: nothing is queued on it)
-    dev_free(h->d_sens);
-    h->cap_sens = 0;
-    HIPCHK(hipMalloc(&h->d_sens, (n_g + n_s + n_k) * sizeof(double)));
-    h->cap_sens = n_g + n_s + n_k;
-  }
-  int call_xbnd = 0;
-  if (lbw || ubw)
-    if (int r = stage_call_bounds(h, lbw, ubw, &call_xbnd)) return r;
-  double *d_gw = h->d_sens, *d_gs = d_gw + n_g, *d_gk = d_gs + n_s;
-  HIPCHK(hipMemcpyAsync(h->d_P, P, (size_t)B * h->np * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_w, w, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lam, lam_g, (size_t)B * h->ng * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->d_lamx, lam_x, (size_t)B * h->nw * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_gw, gw, n_g * sizeof(double), hipMemcpyHostToDevice, s));
-  mpcx::SolveArgs a = make_args(h, B, {.P = h->d_P});
-  if (lbw || ubw) {  // the call's own bounds come before installed device bounds and the spec's
-    a.lbw = h->d_lbw_call;
-    a.ubw = h->d_ubw_call;
-    a.bnd_row = 0;
-    a.xbnd = call_xbnd;
-  }
-  const mpcx::ModelOps* ops = mpcx::model_ops(a);
-  if (!ops) return fail(MPCX_EINVAL, "no kernel for this model");
-  HIPCHK(ops->sens_mdl_vjp(a, h->d_w, h->d_lam, h->d_lamx, d_gw, m, gThk ? d_gk : nullptr, gTh ? d_gs : nullptr,
-                           h->d_status, s));
-  if (gThk) HIPCHK(hipMemcpyAsync(gThk, d_gk, n_k * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (gTh) HIPCHK(hipMemcpyAsync(gTh, d_gs, n_s * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (flag) HIPCHK(hipMemcpyAsync(flag, h->d_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  const size_t n_g = (size_t)B * m * h->nw, n_s = stage_rows(h, B, m, 0, hops->n_th), n_k = n_s * h->spec.N;
+  return sens_host(h, B, P, w, lam_g, lam_x, lbw, ubw, {{gw, n_g}}, {{gThk, n_k}, {gTh, n_s}}, flag,
+                   [&](const mpcx::ModelOps* ops, const mpcx::SolveArgs& a, const SensStage& st, hipStream_t s) {
+                     return ops->sens_mdl_vjp(a, st.w, st.lam_g, st.lam_x, st.in[0], m, gThk ? st.out[0] : nullptr,
+                                              gTh ? st.out[1] : nullptr, st.flag, s);
+                   });
 }
 
 int mpcx_rk4_sens_dev(mpcx_handle* h, int32_t B, const double* d_X, const double* d_U, const double* d_xr,

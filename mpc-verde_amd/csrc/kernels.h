@@ -2381,116 +2381,90 @@ static hipError_t launch_shift_model(const SolveArgs& a, double* P, const double
   return hipGetLastError();
 }
 
-// sensitivities to x0 (sens.h): always the narrowest lane group, single-wave groups only (the host
-// refuses N >= 64)
+// The sensitivity launches (sens.h): always the narrowest lane group that holds nodes 0..N, single-wave
+// groups only (the host refuses N >= 64), 64 / G instances per block.  Every kernel takes (a, W, LG, LX)
+// and then its own arguments.
+#define MPCX_SENS_LAUNCH(kernel, ...)                                                                              \
+  do {                                                                                                             \
+    if (a.N >= 64) return hipErrorInvalidValue;                                                                    \
+    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;                                                              \
+    const dim3 blocks((unsigned)(((long)a.B * G + 63) / 64));                                                      \
+    if (G == 16) hipLaunchKernelGGL((kernel<Model, 16>), blocks, dim3(64), 0, stream, a, W, LG, LX, __VA_ARGS__);      \
+    else if (G == 32) hipLaunchKernelGGL((kernel<Model, 32>), blocks, dim3(64), 0, stream, a, W, LG, LX, __VA_ARGS__); \
+    else hipLaunchKernelGGL((kernel<Model, 64>), blocks, dim3(64), 0, stream, a, W, LG, LX, __VA_ARGS__);              \
+    return hipGetLastError();                                                                                      \
+  } while (0)
+
+// sensitivities to x0 (sens_kernel)
 template <class Model>
 static hipError_t launch_sens_model(const SolveArgs& a, const double* W, const double* LG, const double* LX, double* DW,
                                     double* K0, int32_t* FLAG, hipStream_t stream) {
-  if (a.N >= 64) return hipErrorInvalidValue;
-  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-  const int blocks = (int)(((long)a.B * G + 63) / 64);
-  if (G == 16) hipLaunchKernelGGL((sens_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DW, K0, FLAG);
-  else if (G == 32) hipLaunchKernelGGL((sens_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DW, K0, FLAG);
-  else hipLaunchKernelGGL((sens_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DW, K0, FLAG);
-  return hipGetLastError();
+  MPCX_SENS_LAUNCH(sens_kernel, DW, K0, FLAG);
 }
 
-// directional sensitivities to the parameter row (sens.h sens_p_kernel): the same lane groups; m
-// directions per instance, 1 <= m <= NX.  A model without a reference tangent (its stage row enters
-// the dynamics) has no kernel: the host refuses it first.
+// directional sensitivities to the parameter row (sens_p_kernel) and their adjoint (sens_vjp_kernel): m
+// directions / cotangents per instance, 1 <= m <= NX.  A model without a reference tangent (its stage
+// row enters the dynamics) has no kernel: the host refuses it first.
 template <class Model>
 static hipError_t launch_sens_p_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
                                       const double* DP, int m, double* DW, int32_t* FLAG, hipStream_t stream) {
   if constexpr (!RefTangentOf<Model>::value) {
     return hipErrorInvalidValue;
   } else {
-    if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
-    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-    const int blocks = (int)(((long)a.B * G + 63) / 64);
-    if (G == 16) hipLaunchKernelGGL((sens_p_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DP, m, DW, FLAG);
-    else if (G == 32) hipLaunchKernelGGL((sens_p_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DP, m, DW, FLAG);
-    else hipLaunchKernelGGL((sens_p_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DP, m, DW, FLAG);
-    return hipGetLastError();
+    if (m < 1 || m > Model::NX) return hipErrorInvalidValue;
+    MPCX_SENS_LAUNCH(sens_p_kernel, DP, m, DW, FLAG);
   }
 }
 
-// adjoint sensitivities (sens.h sens_vjp_kernel): the same lane groups; m cotangents per instance,
-// 1 <= m <= NX.  No kernel for a model without a reference tangent, as for sens_p.
 template <class Model>
 static hipError_t launch_sens_vjp_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
                                         const double* GW, int m, double* GP, int32_t* FLAG, hipStream_t stream) {
   if constexpr (!RefTangentOf<Model>::value) {
     return hipErrorInvalidValue;
   } else {
-    if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
-    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-    const int blocks = (int)(((long)a.B * G + 63) / 64);
-    if (G == 16) hipLaunchKernelGGL((sens_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GP, FLAG);
-    else if (G == 32) hipLaunchKernelGGL((sens_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GP, FLAG);
-    else hipLaunchKernelGGL((sens_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GP, FLAG);
-    return hipGetLastError();
+    if (m < 1 || m > Model::NX) return hipErrorInvalidValue;
+    MPCX_SENS_LAUNCH(sens_vjp_kernel, GW, m, GP, FLAG);
   }
 }
 
-// sensitivities to the box bounds (sens.h sens_bnd_kernel, sens_bnd_vjp_kernel): the same lane groups;
-// m directions / cotangents per instance, 1 <= m <= NX.  Every model has them (no reference hook).
+// sensitivities to the box bounds (sens_bnd_kernel, sens_bnd_vjp_kernel): m directions / cotangents per
+// instance, 1 <= m <= NX.  Every model has them (no reference hook).
 template <class Model>
 static hipError_t launch_sens_bnd_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
                                         const double* DLB, const double* DUB, int m, double* DW, int32_t* FLAG,
                                         hipStream_t stream) {
-  if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
-  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-  const int blocks = (int)(((long)a.B * G + 63) / 64);
-  if (G == 16) hipLaunchKernelGGL((sens_bnd_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DLB, DUB, m, DW, FLAG);
-  else if (G == 32) hipLaunchKernelGGL((sens_bnd_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DLB, DUB, m, DW, FLAG);
-  else hipLaunchKernelGGL((sens_bnd_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DLB, DUB, m, DW, FLAG);
-  return hipGetLastError();
+  if (m < 1 || m > Model::NX) return hipErrorInvalidValue;
+  MPCX_SENS_LAUNCH(sens_bnd_kernel, DLB, DUB, m, DW, FLAG);
 }
 
 template <class Model>
 static hipError_t launch_sens_bnd_vjp_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
                                             const double* GW, int m, double* GLB, double* GUB, int32_t* FLAG,
                                             hipStream_t stream) {
-  if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
-  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-  const int blocks = (int)(((long)a.B * G + 63) / 64);
-  if (G == 16) hipLaunchKernelGGL((sens_bnd_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GLB, GUB, FLAG);
-  else if (G == 32) hipLaunchKernelGGL((sens_bnd_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GLB, GUB, FLAG);
-  else hipLaunchKernelGGL((sens_bnd_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GLB, GUB, FLAG);
-  return hipGetLastError();
+  if (m < 1 || m > Model::NX) return hipErrorInvalidValue;
+  MPCX_SENS_LAUNCH(sens_bnd_vjp_kernel, GW, m, GLB, GUB, FLAG);
 }
 
-// sensitivities to the cost weights (sens.h sens_wt_kernel, sens_wt_vjp_kernel): the same lane groups;
-// m directions / cotangents per instance, 1 <= m <= NX; a weight row has Model::NWT entries
+// sensitivities to the cost weights (sens_wt_kernel, sens_wt_vjp_kernel): m directions / cotangents per
+// instance, 1 <= m <= NX; a weight row has Model::NWT entries
 template <class Model>
 static hipError_t launch_sens_wt_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
                                        const double* DWT, int per_stage, int m, double* DW, int32_t* FLAG,
                                        hipStream_t stream) {
-  if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
-  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-  const int blocks = (int)(((long)a.B * G + 63) / 64);
-  const int ps = per_stage ? 1 : 0;
-  if (G == 16) hipLaunchKernelGGL((sens_wt_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DWT, ps, m, DW, FLAG);
-  else if (G == 32) hipLaunchKernelGGL((sens_wt_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DWT, ps, m, DW, FLAG);
-  else hipLaunchKernelGGL((sens_wt_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DWT, ps, m, DW, FLAG);
-  return hipGetLastError();
+  if (m < 1 || m > Model::NX) return hipErrorInvalidValue;
+  MPCX_SENS_LAUNCH(sens_wt_kernel, DWT, per_stage ? 1 : 0, m, DW, FLAG);
 }
 
 template <class Model>
 static hipError_t launch_sens_wt_vjp_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
                                            const double* GW, int m, double* GWK, double* GWS, int32_t* FLAG,
                                            hipStream_t stream) {
-  if (a.N >= 64 || m < 1 || m > Model::NX || (!GWK && !GWS)) return hipErrorInvalidValue;
-  const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-  const int blocks = (int)(((long)a.B * G + 63) / 64);
-  if (G == 16) hipLaunchKernelGGL((sens_wt_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GWK, GWS, FLAG);
-  else if (G == 32) hipLaunchKernelGGL((sens_wt_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GWK, GWS, FLAG);
-  else hipLaunchKernelGGL((sens_wt_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GWK, GWS, FLAG);
-  return hipGetLastError();
+  if (m < 1 || m > Model::NX || (!GWK && !GWS)) return hipErrorInvalidValue;
+  MPCX_SENS_LAUNCH(sens_wt_vjp_kernel, GW, m, GWK, GWS, FLAG);
 }
 
-// sensitivities to the model row (sens.h sens_mdl_kernel, sens_mdl_vjp_kernel): the same lane groups;
-// m directions / cotangents per instance, 1 <= m <= NX; a model row has Model::NTH entries (none: no launch)
+// sensitivities to the model row (sens_mdl_kernel, sens_mdl_vjp_kernel): m directions / cotangents per
+// instance, 1 <= m <= NX; a model row has Model::NTH entries (none: no kernel)
 template <class Model>
 static hipError_t launch_sens_mdl_model(const SolveArgs& a, const double* W, const double* LG, const double* LX,
                                         const double* DTH, int per_stage, int m, double* DW, int32_t* FLAG,
@@ -2498,14 +2472,8 @@ static hipError_t launch_sens_mdl_model(const SolveArgs& a, const double* W, con
   if constexpr (Model::NTH == 0) {
     return hipErrorInvalidValue;
   } else {
-    if (a.N >= 64 || m < 1 || m > Model::NX) return hipErrorInvalidValue;
-    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-    const int blocks = (int)(((long)a.B * G + 63) / 64);
-    const int ps = per_stage ? 1 : 0;
-    if (G == 16) hipLaunchKernelGGL((sens_mdl_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DTH, ps, m, DW, FLAG);
-    else if (G == 32) hipLaunchKernelGGL((sens_mdl_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DTH, ps, m, DW, FLAG);
-    else hipLaunchKernelGGL((sens_mdl_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, DTH, ps, m, DW, FLAG);
-    return hipGetLastError();
+    if (m < 1 || m > Model::NX) return hipErrorInvalidValue;
+    MPCX_SENS_LAUNCH(sens_mdl_kernel, DTH, per_stage ? 1 : 0, m, DW, FLAG);
   }
 }
 
@@ -2516,15 +2484,11 @@ static hipError_t launch_sens_mdl_vjp_model(const SolveArgs& a, const double* W,
   if constexpr (Model::NTH == 0) {
     return hipErrorInvalidValue;
   } else {
-    if (a.N >= 64 || m < 1 || m > Model::NX || (!GTK && !GTS)) return hipErrorInvalidValue;
-    const int G = a.N < 16 ? 16 : a.N < 32 ? 32 : 64;
-    const int blocks = (int)(((long)a.B * G + 63) / 64);
-    if (G == 16) hipLaunchKernelGGL((sens_mdl_vjp_kernel<Model, 16>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GTK, GTS, FLAG);
-    else if (G == 32) hipLaunchKernelGGL((sens_mdl_vjp_kernel<Model, 32>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GTK, GTS, FLAG);
-    else hipLaunchKernelGGL((sens_mdl_vjp_kernel<Model, 64>), dim3(blocks), dim3(64), 0, stream, a, W, LG, LX, GW, m, GTK, GTS, FLAG);
-    return hipGetLastError();
+    if (m < 1 || m > Model::NX || (!GTK && !GTS)) return hipErrorInvalidValue;
+    MPCX_SENS_LAUNCH(sens_mdl_vjp_kernel, GW, m, GTK, GTS, FLAG);
   }
 }
+#undef MPCX_SENS_LAUNCH
 
 #ifdef MPCX_STAMPS
 // diagnostic build: this unit's setters of its own copies of the stamp/counter pointers

@@ -18,11 +18,56 @@ multipliers (include/mpcx.h, mpcx_sens_x0).
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from .device import DeviceLoop
 
 __all__ = ["MPCFunction", "MPCBoundsFunction", "MPCWeightsFunction", "MPCParFunction", "solve_differentiable"]
+
+
+@contextlib.contextmanager
+def _on_loop_stream(loop):
+    """The body runs with the loop's stream current, ordered after the work queued so far on the caller's
+    stream, which in turn is ordered after the body's work (device-side ordering only: nothing waits on
+    the host)."""
+    cur = torch.cuda.current_stream(loop.device)
+    loop.stream.wait_stream(cur)
+    with torch.cuda.stream(loop.stream):
+        yield
+    cur.wait_stream(loop.stream)
+
+
+def _forward(ctx, P, loop, zero_irregular, *also_saved):
+    """The four classes' forward, on the loop's stream: copies P into the loop, enqueues ``loop.solve()``,
+    saves copies of the point (P, w, lam, lamx), then ``also_saved``, and returns a copy of w."""
+    loop.P.copy_(P.detach(), non_blocking=True)
+    loop.solve()
+    point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
+    ctx.loop, ctx.zero_irregular = loop, zero_irregular
+    ctx.save_for_backward(*point, *also_saved)
+    return point[1].clone()
+
+
+def _backward(ctx, gw, point, own=None):
+    """The four classes' backward, on the loop's stream, with dL/dw as the one cotangent: own(g) makes
+    the class's own launch and returns (*rows, flag), rows being (B, .) gradients; ``loop.sens_vjp`` is
+    launched for P's rows when there is no own launch or P requires a gradient.  The rows of an
+    instance flagged irregular are zeroed if the forward asked for it.  Returns (gP or None, rows)."""
+    g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
+    rows, flag, gP = [], None, None
+    if own is not None:
+        *rows, flag = own(g)
+    if own is None or ctx.needs_input_grad[0]:
+        gP, flag_p = ctx.loop.sens_vjp(g, point=point)  # (the same factors: the same flag)
+        gP, flag = gP[:, 0], flag_p if flag is None else flag
+    if ctx.zero_irregular:
+        bad = flag[:, None] != 0
+        rows = [torch.where(bad, torch.zeros_like(t), t) for t in rows]
+        if gP is not None:
+            gP = torch.where(bad, torch.zeros_like(gP), gP)
+    return gP, rows
 
 
 class MPCFunction(torch.autograd.Function):
@@ -32,30 +77,13 @@ class MPCFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, P, loop, zero_irregular):
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)  # (device-side ordering only: nothing waits on the host)
-        with torch.cuda.stream(loop.stream):
-            loop.P.copy_(P.detach(), non_blocking=True)
-            loop.solve()
-            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
-            w = point[1].clone()
-        cur.wait_stream(loop.stream)
-        ctx.loop, ctx.zero_irregular = loop, zero_irregular
-        ctx.save_for_backward(*point)
-        return w
+        with _on_loop_stream(loop):
+            return _forward(ctx, P, loop, zero_irregular)
 
     @staticmethod
     def backward(ctx, gw):
-        loop = ctx.loop
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)
-        with torch.cuda.stream(loop.stream):
-            g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
-            gP, flag = loop.sens_vjp(g, point=ctx.saved_tensors)
-            gP = gP[:, 0]
-            if ctx.zero_irregular:
-                gP = torch.where(flag[:, None] != 0, torch.zeros_like(gP), gP)
-        cur.wait_stream(loop.stream)
+        with _on_loop_stream(ctx.loop):
+            gP, _ = _backward(ctx, gw, ctx.saved_tensors)
         return gP, None, None
 
 
@@ -74,21 +102,11 @@ class MPCBoundsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, P, lbw, ubw, loop, zero_irregular):
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)
-        with torch.cuda.stream(loop.stream):
+        with _on_loop_stream(loop):
             lb, ub = lbw.detach().clone(), ubw.detach().clone()
-        loop.set_bounds(lb, ub)
-        state = loop.solver._dev_bounds
-        with torch.cuda.stream(loop.stream):
-            loop.P.copy_(P.detach(), non_blocking=True)
-            loop.solve()
-            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
-            w = point[1].clone()
-        cur.wait_stream(loop.stream)
-        ctx.loop, ctx.zero_irregular, ctx.state = loop, zero_irregular, state
-        ctx.save_for_backward(*point, lb, ub)
-        return w
+            loop.set_bounds(lb, ub)
+            ctx.state = loop.solver._dev_bounds
+            return _forward(ctx, P, loop, zero_irregular, lb, ub)
 
     @staticmethod
     def backward(ctx, gw):
@@ -98,30 +116,22 @@ class MPCBoundsFunction(torch.autograd.Function):
         moved = before is not ctx.state
         if moved:  # the forward's bounds, for the launches below
             loop.set_bounds(lb, ub)
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)
-        gP = None
-        try:
-            with torch.cuda.stream(loop.stream):
-                g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
-                gl, gu, flag = loop.sens_bounds_vjp(g, point=point)
-                gl, gu = gl[:, 0], gu[:, 0]
-                if ctx.needs_input_grad[0]:
-                    gP, _ = loop.sens_vjp(g, point=point)  # (the same factors: the same flag)
-                    gP = gP[:, 0]
-                pd = getattr(loop.solver, "_pad", None)
-                if pd is not None:  # the bounds were given in the model's own layout
-                    idx = torch.from_numpy(pd.w_idx).to(loop.device)
-                    gl, gu = gl[:, idx], gu[:, idx]
-                if ctx.zero_irregular:
-                    bad = flag[:, None] != 0
-                    gl, gu = (torch.where(bad, torch.zeros_like(t), t) for t in (gl, gu))
-                    if gP is not None:
-                        gP = torch.where(bad, torch.zeros_like(gP), gP)
-        finally:
-            if moved:  # (stream-ordered after the launches; the validation waits for the stream)
-                loop.solver._install_bounds(before, loop.stream.cuda_stream if before is not None else None)
-        cur.wait_stream(loop.stream)
+
+        def own(g):
+            gl, gu, flag = loop.sens_bounds_vjp(g, point=point)
+            gl, gu = gl[:, 0], gu[:, 0]
+            pd = getattr(loop.solver, "_pad", None)
+            if pd is not None:  # the bounds were given in the model's own layout
+                idx = torch.from_numpy(pd.w_idx).to(loop.device)
+                gl, gu = gl[:, idx], gu[:, idx]
+            return gl, gu, flag
+
+        with _on_loop_stream(loop):
+            try:
+                gP, (gl, gu) = _backward(ctx, gw, point, own)
+            finally:
+                if moved:  # (stream-ordered after the launches; the validation waits for the stream)
+                    loop.solver._install_bounds(before, loop.stream.cuda_stream if before is not None else None)
         return gP, gl if ctx.needs_input_grad[1] else None, gu if ctx.needs_input_grad[2] else None, None, None
 
 
@@ -143,17 +153,9 @@ class MPCWeightsFunction(torch.autograd.Function):
     def forward(ctx, P, Q, R, loop, zero_irregular):
         q, r = (tuple(float(v) for v in t.detach().cpu().tolist()) for t in (Q, R))  # (the one host read)
         loop.solver.set_weights(q, r)
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)
-        with torch.cuda.stream(loop.stream):
-            loop.P.copy_(P.detach(), non_blocking=True)
-            loop.solve()
-            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
-            w = point[1].clone()
-        cur.wait_stream(loop.stream)
-        ctx.loop, ctx.zero_irregular, ctx.weights = loop, zero_irregular, (q, r)
-        ctx.save_for_backward(*point)
-        return w
+        ctx.weights = (q, r)
+        with _on_loop_stream(loop):
+            return _forward(ctx, P, loop, zero_irregular)
 
     @staticmethod
     def backward(ctx, gw):
@@ -163,29 +165,20 @@ class MPCWeightsFunction(torch.autograd.Function):
         moved = before != ctx.weights
         if moved:  # the forward's weights, for the launches below (launch arguments: taken at the call)
             solver.set_weights(*ctx.weights)
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)
-        gP = None
         nx = solver.ocp.nx
-        try:
-            with torch.cuda.stream(loop.stream):
-                g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
-                _, gs, flag = loop.sens_weights_vjp(g, point=point, per_stage=False)
-                gs = gs[:, 0]
-                if ctx.needs_input_grad[0]:
-                    gP, _ = loop.sens_vjp(g, point=point)  # (the same factors: the same flag)
-                    gP = gP[:, 0]
-                if ctx.zero_irregular:
-                    bad = flag[:, None] != 0
-                    gs = torch.where(bad, torch.zeros_like(gs), gs)
-                    if gP is not None:
-                        gP = torch.where(bad, torch.zeros_like(gP), gP)
+
+        def own(g):
+            _, gs, flag = loop.sens_weights_vjp(g, point=point, per_stage=False)
+            return gs[:, 0], flag
+
+        with _on_loop_stream(loop):
+            try:
+                gP, (gs,) = _backward(ctx, gw, point, own)
                 gs = gs.sum(dim=0)
                 gQ, gR = gs[:nx].contiguous(), gs[nx:].contiguous()
-        finally:
-            if moved:
-                solver.set_weights(*before)
-        cur.wait_stream(loop.stream)
+            finally:
+                if moved:
+                    solver.set_weights(*before)
         return gP, gQ if ctx.needs_input_grad[1] else None, gR if ctx.needs_input_grad[2] else None, None, None
 
 
@@ -206,17 +199,9 @@ class MPCParFunction(torch.autograd.Function):
     def forward(ctx, P, par, loop, zero_irregular):
         pv = tuple(float(v) for v in par.detach().cpu().tolist())  # (the one host read)
         loop.solver.set_par(pv)
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)
-        with torch.cuda.stream(loop.stream):
-            loop.P.copy_(P.detach(), non_blocking=True)
-            loop.solve()
-            point = tuple(t.clone() for t in (loop.P, loop.w, loop.lam, loop.lamx))
-            w = point[1].clone()
-        cur.wait_stream(loop.stream)
-        ctx.loop, ctx.zero_irregular, ctx.par = loop, zero_irregular, pv
-        ctx.save_for_backward(*point)
-        return w
+        ctx.par = pv
+        with _on_loop_stream(loop):
+            return _forward(ctx, P, loop, zero_irregular)
 
     @staticmethod
     def backward(ctx, gw):
@@ -226,27 +211,18 @@ class MPCParFunction(torch.autograd.Function):
         moved = before != ctx.par
         if moved:  # the forward's constants, for the launches below (launch arguments: taken at the call)
             solver.set_par(ctx.par)
-        cur = torch.cuda.current_stream(loop.device)
-        loop.stream.wait_stream(cur)
-        gP = None
-        try:
-            with torch.cuda.stream(loop.stream):
-                g = gw.detach().to(torch.float64).contiguous().unsqueeze(1)  # one cotangent: m = 1
-                _, gs, flag = loop.sens_model_vjp(g, point=point, per_stage=False)
-                gs = gs[:, 0]
-                if ctx.needs_input_grad[0]:
-                    gP, _ = loop.sens_vjp(g, point=point)  # (the same factors: the same flag)
-                    gP = gP[:, 0]
-                if ctx.zero_irregular:
-                    bad = flag[:, None] != 0
-                    gs = torch.where(bad, torch.zeros_like(gs), gs)
-                    if gP is not None:
-                        gP = torch.where(bad, torch.zeros_like(gP), gP)
+
+        def own(g):
+            _, gs, flag = loop.sens_model_vjp(g, point=point, per_stage=False)
+            return gs[:, 0], flag
+
+        with _on_loop_stream(loop):
+            try:
+                gP, (gs,) = _backward(ctx, gw, point, own)
                 gpar = gs.sum(dim=0).contiguous()
-        finally:
-            if moved:
-                solver.set_par(before)
-        cur.wait_stream(loop.stream)
+            finally:
+                if moved:
+                    solver.set_par(before)
         return gP, gpar if ctx.needs_input_grad[1] else None, None, None
 
 

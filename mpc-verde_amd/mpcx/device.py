@@ -108,6 +108,54 @@ class DeviceLoop:
                                       _ptr(self.lam) if d else None, _ptr(self.lam0) if d else None,
                                       _ptr(self.lamx) if d else None, _ptr(self.lamx0) if d else None, s))
 
+    def _point(self, point):
+        n_p, nw, ng = self.P.shape[1], self.solver._h.n_w, self.lam.shape[1]
+        if point is None:
+            return self.P, self.w, self.lam, self.lamx
+        if len(point) != 4:
+            raise ValueError("point: expected (P, w, lam, lamx)")
+        for t, name, n in zip(point, ("point P", "point w", "point lam", "point lamx"), (n_p, nw, ng, nw)):
+            _check(t, name, torch.float64, (self.B, n), self.device)
+        return point
+
+    def _cotangents(self, gw):
+        """The cotangents of a ``*_vjp`` call, (B, m, n_w) with 1 <= m <= nx: validated; returns m."""
+        nw, nx = self.solver._h.n_w, self._knx
+        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
+            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
+        _check(gw, "gw", torch.float64, (self.B, gw.shape[1], nw), self.device)
+        return gw.shape[1]
+
+    def _stage_rows(self, d, name, n):
+        """The directions of weight or model rows (n entries each), (B, m, n) for rows used at every
+        stage or (B, m, N, n) for one row per stage, 1 <= m <= nx: validated; returns (m, per_stage)."""
+        nx, N = self._knx, self.solver.ocp.N
+        if not isinstance(d, torch.Tensor) or d.dim() not in (3, 4) or not 1 <= d.shape[1] <= nx:
+            raise ValueError(f"{name}: expected a ({self.B}, m, {n}) or ({self.B}, m, {N}, {n}) tensor with "
+                             f"1 <= m <= {nx}")
+        m, per_stage = d.shape[1], int(d.dim() == 4)
+        _check(d, name, torch.float64, (self.B, m, N, n) if per_stage else (self.B, m, n), self.device)
+        return m, per_stage
+
+    def _sens(self, entry, point, args, flag_out, *outs):
+        """What the sensitivity methods share once their inputs are validated: resolve ``point``, take
+        the outputs ``outs`` = (name, tensor given or None, shape[, allocate]) and the flag -- one not
+        given is allocated on the loop's stream (or stays None with allocate False: not computed), one
+        given is validated -- and enqueue the C entry point ``entry`` (point, *args, outputs, flag,
+        stream) on the loop's stream.  Returns (*outputs, flag)."""
+        point = self._point(point)
+        outs = [o if len(o) == 4 else o + (True,) for o in outs] + [("flag_out", flag_out, (self.B,), True)]
+        dtypes = [torch.float64] * (len(outs) - 1) + [torch.int32]
+        with torch.cuda.stream(self.stream):
+            ts = [torch.empty(shape, dtype=dt, device=self.device) if t is None and alloc else t
+                  for (_, t, shape, alloc), dt in zip(outs, dtypes)]
+        for (name, _, shape, _), t, dt in zip(outs, ts, dtypes):
+            if t is not None:
+                _check(t, name, dt, shape, self.device)
+        _lib.check(getattr(_lib.load(), entry)(self.solver._h.ptr, self.B, *map(_ptr, point), *args, *map(_ptr, ts),
+                                               ctypes_void(self.stream.cuda_stream)))
+        return tuple(ts)
+
     def sens_x0(self, dw_out=None, K0_out=None, flag_out=None):
         """Enqueue one sensitivity launch (mpcx_sens_x0_dev) at the loop's resident P, w, lam, lamx:
         dw_dx0 (B, n_w, nx), K0 (B, nu, nx) -- the feedback gain, u ~ u0* + K0 (x - x0) -- and
@@ -116,18 +164,8 @@ class DeviceLoop:
         allocated; returns (dw_dx0, K0, flag) without waiting for the stream.  After ``solve()``
         P still holds the x0 the solution belongs to; ``step()`` has already advanced it."""
         nw, nx, nu = self.solver._h.n_w, self._knx, self.solver.ocp.nu
-        with torch.cuda.stream(self.stream):
-            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
-            dw = new((self.B, nw, nx), torch.float64) if dw_out is None else dw_out
-            K0 = new((self.B, nu, nx), torch.float64) if K0_out is None else K0_out
-            flag = new((self.B,), torch.int32) if flag_out is None else flag_out
-        _check(dw, "dw_out", torch.float64, (self.B, nw, nx), self.device)
-        _check(K0, "K0_out", torch.float64, (self.B, nu, nx), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_x0_dev(self.solver._h.ptr, self.B, _ptr(self.P), _ptr(self.w), _ptr(self.lam),
-                                                _ptr(self.lamx), _ptr(dw), _ptr(K0), _ptr(flag),
-                                                ctypes_void(self.stream.cuda_stream)))
-        return dw, K0, flag
+        return self._sens("mpcx_sens_x0_dev", None, (), flag_out,
+                          ("dw_out", dw_out, (self.B, nw, nx)), ("K0_out", K0_out, (self.B, nu, nx)))
 
     def sens_p(self, dP, dw_out=None, flag_out=None):
         """Enqueue one parameter-sensitivity launch (mpcx_sens_p_dev) at the loop's resident P, w, lam,
@@ -141,15 +179,7 @@ class DeviceLoop:
             raise ValueError(f"dP: expected a ({self.B}, m, {self.P.shape[1]}) tensor with 1 <= m <= {nx}")
         m = dP.shape[1]
         _check(dP, "dP", torch.float64, (self.B, m, self.P.shape[1]), self.device)
-        with torch.cuda.stream(self.stream):
-            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
-        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_p_dev(self.solver._h.ptr, self.B, _ptr(self.P), _ptr(self.w), _ptr(self.lam),
-                                               _ptr(self.lamx), _ptr(dP), m, _ptr(dw), _ptr(flag),
-                                               ctypes_void(self.stream.cuda_stream)))
-        return dw, flag
+        return self._sens("mpcx_sens_p_dev", None, (_ptr(dP), m), flag_out, ("dw_out", dw_out, (self.B, nw, m)))
 
     def sens_vjp(self, gw, gP_out=None, flag_out=None, point=None):
         """Enqueue one adjoint-sensitivity launch (mpcx_sens_vjp_dev) at the loop's resident P, w, lam,
@@ -160,36 +190,9 @@ class DeviceLoop:
         resident ones' shapes to take the point from instead (the next solve overwrites the resident
         ones; a saved point does not move).  Tensors given are written in place, the others are
         allocated; returns (gP, flag) without waiting for the stream."""
-        nw, nx, n_p, ng = self.solver._h.n_w, self._knx, self.P.shape[1], self.lam.shape[1]
-        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
-            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
-        m = gw.shape[1]
-        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
-        if point is None:
-            point = (self.P, self.w, self.lam, self.lamx)
-        elif len(point) != 4:
-            raise ValueError("point: expected (P, w, lam, lamx)")
-        for t, name, n in zip(point, ("point P", "point w", "point lam", "point lamx"), (n_p, nw, ng, nw)):
-            _check(t, name, torch.float64, (self.B, n), self.device)
-        with torch.cuda.stream(self.stream):
-            gP = torch.empty((self.B, m, n_p), dtype=torch.float64, device=self.device) if gP_out is None else gP_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
-        _check(gP, "gP_out", torch.float64, (self.B, m, n_p), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
-                                                 _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gP), _ptr(flag),
-                                                 ctypes_void(self.stream.cuda_stream)))
-        return gP, flag
-
-    def _point(self, point):
-        n_p, nw, ng = self.P.shape[1], self.solver._h.n_w, self.lam.shape[1]
-        if point is None:
-            return self.P, self.w, self.lam, self.lamx
-        if len(point) != 4:
-            raise ValueError("point: expected (P, w, lam, lamx)")
-        for t, name, n in zip(point, ("point P", "point w", "point lam", "point lamx"), (n_p, nw, ng, nw)):
-            _check(t, name, torch.float64, (self.B, n), self.device)
-        return point
+        m = self._cotangents(gw)
+        return self._sens("mpcx_sens_vjp_dev", point, (_ptr(gw), m), flag_out,
+                          ("gP_out", gP_out, (self.B, m, self.P.shape[1])))
 
     def sens_bounds(self, dlbw, dubw, dw_out=None, flag_out=None, point=None):
         """Enqueue one bound-sensitivity launch (mpcx_sens_bounds_dev) at the loop's resident P, w, lam,
@@ -206,17 +209,10 @@ class DeviceLoop:
         m = given.shape[1]
         with torch.cuda.stream(self.stream):
             dlbw, dubw = (torch.zeros_like(given) if t is None else t for t in (dlbw, dubw))
-            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
         _check(dlbw, "dlbw", torch.float64, (self.B, m, nw), self.device)
         _check(dubw, "dubw", torch.float64, (self.B, m, nw), self.device)
-        point = self._point(point)
-        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_bounds_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
-                                                    _ptr(point[2]), _ptr(point[3]), _ptr(dlbw), _ptr(dubw), m, _ptr(dw),
-                                                    _ptr(flag), ctypes_void(self.stream.cuda_stream)))
-        return dw, flag
+        return self._sens("mpcx_sens_bounds_dev", point, (_ptr(dlbw), _ptr(dubw), m), flag_out,
+                          ("dw_out", dw_out, (self.B, nw, m)))
 
     def sens_bounds_vjp(self, gw, glbw_out=None, gubw_out=None, flag_out=None, point=None):
         """Enqueue one launch of the reverse mode of :meth:`sens_bounds` (mpcx_sens_bounds_vjp_dev): gw
@@ -225,24 +221,9 @@ class DeviceLoop:
         written: 0 where there is no finite bound), and flag (B,) int32.  point = (P, w, lam, lamx): as
         :meth:`sens_vjp`; the bounds are always the ones in force at the call.  Returns (glbw, gubw,
         flag) without waiting for the stream."""
-        nw, nx = self.solver._h.n_w, self._knx
-        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
-            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
-        m = gw.shape[1]
-        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
-        point = self._point(point)
-        with torch.cuda.stream(self.stream):
-            new = lambda: torch.empty((self.B, m, nw), dtype=torch.float64, device=self.device)  # noqa: E731
-            gl = new() if glbw_out is None else glbw_out
-            gu = new() if gubw_out is None else gubw_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
-        _check(gl, "glbw_out", torch.float64, (self.B, m, nw), self.device)
-        _check(gu, "gubw_out", torch.float64, (self.B, m, nw), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_bounds_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
-                                                        _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gl), _ptr(gu),
-                                                        _ptr(flag), ctypes_void(self.stream.cuda_stream)))
-        return gl, gu, flag
+        m, nw = self._cotangents(gw), self.solver._h.n_w
+        return self._sens("mpcx_sens_bounds_vjp_dev", point, (_ptr(gw), m), flag_out,
+                          ("glbw_out", glbw_out, (self.B, m, nw)), ("gubw_out", gubw_out, (self.B, m, nw)))
 
     def sens_weights(self, dW, dw_out=None, flag_out=None, point=None):
         """Enqueue one weight-sensitivity launch (mpcx_sens_weights_dev) at the loop's resident P, w, lam,
@@ -252,22 +233,9 @@ class DeviceLoop:
         used at every stage or (B, m, N, n_wt) for one row per stage, gives dw (B, n_w, m) and flag (B,)
         int32 (1 = irregular instance, NaN outputs).  point: as :meth:`sens_vjp`.  Tensors given are
         written in place, the others are allocated; returns (dw, flag) without waiting for the stream."""
-        nw, nx, N, n_wt = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.weight_dims()
-        if not isinstance(dW, torch.Tensor) or dW.dim() not in (3, 4) or not 1 <= dW.shape[1] <= nx:
-            raise ValueError(f"dW: expected a ({self.B}, m, {n_wt}) or ({self.B}, m, {N}, {n_wt}) tensor with "
-                             f"1 <= m <= {nx}")
-        m, per_stage = dW.shape[1], int(dW.dim() == 4)
-        _check(dW, "dW", torch.float64, (self.B, m, N, n_wt) if per_stage else (self.B, m, n_wt), self.device)
-        point = self._point(point)
-        with torch.cuda.stream(self.stream):
-            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
-        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_weights_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
-                                                     _ptr(point[2]), _ptr(point[3]), _ptr(dW), per_stage, m, _ptr(dw),
-                                                     _ptr(flag), ctypes_void(self.stream.cuda_stream)))
-        return dw, flag
+        m, per_stage = self._stage_rows(dW, "dW", self.solver._h.weight_dims())
+        return self._sens("mpcx_sens_weights_dev", point, (_ptr(dW), per_stage, m), flag_out,
+                          ("dw_out", dw_out, (self.B, self.solver._h.n_w, m)))
 
     def sens_weights_vjp(self, gw, gWk_out=None, gW_out=None, flag_out=None, point=None, per_stage=True):
         """Enqueue one launch of the reverse mode of :meth:`sens_weights` (mpcx_sens_weights_vjp_dev): gw
@@ -277,25 +245,10 @@ class DeviceLoop:
         flag (B,) int32, in the kernel's layout.  point = (P, w, lam, lamx): as :meth:`sens_vjp`; the
         weights and bounds are the ones in force at the call.  Returns (gWk, gW, flag) without waiting
         for the stream."""
-        nw, nx, N, n_wt = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.weight_dims()
-        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
-            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
-        m = gw.shape[1]
-        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
-        point = self._point(point)
-        with torch.cuda.stream(self.stream):
-            new = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)  # noqa: E731
-            gk = gWk_out if gWk_out is not None else (new(self.B, m, N, n_wt) if per_stage else None)
-            gs = new(self.B, m, n_wt) if gW_out is None else gW_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
-        if gk is not None:
-            _check(gk, "gWk_out", torch.float64, (self.B, m, N, n_wt), self.device)
-        _check(gs, "gW_out", torch.float64, (self.B, m, n_wt), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_weights_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
-                                                         _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gk),
-                                                         _ptr(gs), _ptr(flag), ctypes_void(self.stream.cuda_stream)))
-        return gk, gs, flag
+        N, n_wt = self.solver.ocp.N, self.solver._h.weight_dims()
+        m = self._cotangents(gw)
+        return self._sens("mpcx_sens_weights_vjp_dev", point, (_ptr(gw), m), flag_out,
+                          ("gWk_out", gWk_out, (self.B, m, N, n_wt), per_stage), ("gW_out", gW_out, (self.B, m, n_wt)))
 
     def sens_model(self, dTh, dw_out=None, flag_out=None, point=None):
         """Enqueue one model-sensitivity launch (mpcx_sens_model_dev) at the loop's resident P, w, lam, lamx,
@@ -305,22 +258,9 @@ class DeviceLoop:
         for rows used at every stage or (B, m, N, n_th) for one row per stage, gives dw (B, n_w, m) and flag
         (B,) int32 (1 = irregular instance, NaN outputs).  point: as :meth:`sens_vjp`.  Tensors given are
         written in place, the others are allocated; returns (dw, flag) without waiting for the stream."""
-        nw, nx, N, n_th = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.model_dims()
-        if not isinstance(dTh, torch.Tensor) or dTh.dim() not in (3, 4) or not 1 <= dTh.shape[1] <= nx:
-            raise ValueError(f"dTh: expected a ({self.B}, m, {n_th}) or ({self.B}, m, {N}, {n_th}) tensor with "
-                             f"1 <= m <= {nx}")
-        m, per_stage = dTh.shape[1], int(dTh.dim() == 4)
-        _check(dTh, "dTh", torch.float64, (self.B, m, N, n_th) if per_stage else (self.B, m, n_th), self.device)
-        point = self._point(point)
-        with torch.cuda.stream(self.stream):
-            dw = torch.empty((self.B, nw, m), dtype=torch.float64, device=self.device) if dw_out is None else dw_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
-        _check(dw, "dw_out", torch.float64, (self.B, nw, m), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_model_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
-                                                   _ptr(point[2]), _ptr(point[3]), _ptr(dTh), per_stage, m, _ptr(dw),
-                                                   _ptr(flag), ctypes_void(self.stream.cuda_stream)))
-        return dw, flag
+        m, per_stage = self._stage_rows(dTh, "dTh", self.solver._h.model_dims())
+        return self._sens("mpcx_sens_model_dev", point, (_ptr(dTh), per_stage, m), flag_out,
+                          ("dw_out", dw_out, (self.B, self.solver._h.n_w, m)))
 
     def sens_model_vjp(self, gw, gThk_out=None, gTh_out=None, flag_out=None, point=None, per_stage=True):
         """Enqueue one launch of the reverse mode of :meth:`sens_model` (mpcx_sens_model_vjp_dev): gw
@@ -330,25 +270,11 @@ class DeviceLoop:
         flag (B,) int32, in the kernel's layout.  point = (P, w, lam, lamx): as :meth:`sens_vjp`; the
         constants and bounds are the ones in force at the call.  Returns (gThk, gTh, flag) without waiting
         for the stream."""
-        nw, nx, N, n_th = self.solver._h.n_w, self._knx, self.solver.ocp.N, self.solver._h.model_dims()
-        if not isinstance(gw, torch.Tensor) or gw.dim() != 3 or not 1 <= gw.shape[1] <= nx:
-            raise ValueError(f"gw: expected a ({self.B}, m, {nw}) tensor with 1 <= m <= {nx}")
-        m = gw.shape[1]
-        _check(gw, "gw", torch.float64, (self.B, m, nw), self.device)
-        point = self._point(point)
-        with torch.cuda.stream(self.stream):
-            new = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)  # noqa: E731
-            gk = gThk_out if gThk_out is not None else (new(self.B, m, N, n_th) if per_stage else None)
-            gs = new(self.B, m, n_th) if gTh_out is None else gTh_out
-            flag = torch.empty((self.B,), dtype=torch.int32, device=self.device) if flag_out is None else flag_out
-        if gk is not None:
-            _check(gk, "gThk_out", torch.float64, (self.B, m, N, n_th), self.device)
-        _check(gs, "gTh_out", torch.float64, (self.B, m, n_th), self.device)
-        _check(flag, "flag_out", torch.int32, (self.B,), self.device)
-        _lib.check(_lib.load().mpcx_sens_model_vjp_dev(self.solver._h.ptr, self.B, _ptr(point[0]), _ptr(point[1]),
-                                                       _ptr(point[2]), _ptr(point[3]), _ptr(gw), m, _ptr(gk),
-                                                       _ptr(gs), _ptr(flag), ctypes_void(self.stream.cuda_stream)))
-        return gk, gs, flag
+        N, n_th = self.solver.ocp.N, self.solver._h.model_dims()
+        m = self._cotangents(gw)
+        return self._sens("mpcx_sens_model_vjp_dev", point, (_ptr(gw), m), flag_out,
+                          ("gThk_out", gThk_out, (self.B, m, N, n_th), per_stage),
+                          ("gTh_out", gTh_out, (self.B, m, n_th)))
 
     def set_stage_refs(self, refs):
         """Per-step stage references (tracking, param layout x0_stageref): refs is a

@@ -233,35 +233,19 @@ class Solver:
         indefinite reduced Hessian), whose outputs are NaN.  These are the sensitivities of the barrier
         problem at the multipliers given: the active-set ones to O(mu) at a strictly complementary
         solution.  The single-shooting form gets the rows of its own w, the controls: (B, N nu, nx)."""
-        P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
-        B = P.shape[0]
-        if P.shape[1] != self.n_p:
-            raise ValueError(f"P: expected {self.n_p} columns, got {P.shape[1]}")
-        nw, ng = self._ms_nw, self._ms_ng
-        w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
-                        for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
-        lbw, ubw = _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw")
+        B, point, (lbw, ubw, _) = self._sens_point(P, res, lbw, ubw, instance_bounds=False)
         nx, nu = self.ocp.nx, self.ocp.nu
-        knx = nx
-        pd = self._pad
-        if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
-            P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
-            w, lamx = pd.scatter(w, pd.w_idx, pd.n_w_pad), pd.scatter(lamx, pd.w_idx, pd.n_w_pad)
-            lam = pd.scatter(lam, pd.g_idx, pd.n_g_pad)
-            lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
-            ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
-            nw, knx = pd.n_w_pad, pd.nxp
+        nw, knx, _ = self._kdims
         dw = np.empty((B, nw, knx))
         K0 = np.empty((B, nu, knx))
         flag = np.empty(B, np.int32)
-        _lib.check(_lib.load().mpcx_sens_x0(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam), _lib.dptr(lamx),
-                                            _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(dw), _lib.dptr(K0),
-                                            _lib.iptr(flag)))
+        _lib.check(_lib.load().mpcx_sens_x0(self._h.ptr, B, *map(_lib.dptr, point), _lib.dptr(lbw), _lib.dptr(ubw),
+                                            _lib.dptr(dw), _lib.dptr(K0), _lib.iptr(flag)))
+        pd = self._pad
         if pd is not None:  # the model's own states and inputs only
             dw, K0 = dw[:, pd.w_idx, :nx], K0[:, :, :nx]
         if self.ocp.formulation == "single_shooting":
-            nz = nx + nu
-            dw = dw[:, np.concatenate([nx + nz * k + np.arange(nu) for k in range(self.ocp.N)])]
+            dw = dw[:, self._ss_rows()]
         return {"dw_dx0": np.ascontiguousarray(dw), "K0": np.ascontiguousarray(K0), "flag": flag}
 
     def sens_p(self, P, res, dP, lbw=None, ubw=None):
@@ -276,49 +260,15 @@ class Solver:
         flag 1 marks an irregular instance (NaN outputs), as :meth:`sens_x0`.  The X_0 rows are
         dP[:, :, :nx].  The single-shooting form gets the control rows.  Not for the path-frame
         bicycle (its stage rows enter the dynamics)."""
-        P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
-        B = P.shape[0]
-        if P.shape[1] != self.n_p:
-            raise ValueError(f"P: expected {self.n_p} columns, got {P.shape[1]}")
-        dP = np.asarray(dP, np.float64)
-        if dP.ndim == 2:
-            dP = dP[:, None, :]
-        if dP.ndim != 3 or dP.shape[0] != B or dP.shape[2] != self.n_p or dP.shape[1] < 1:
-            raise ValueError(f"dP: expected ({B}, m, {self.n_p}) or ({B}, {self.n_p}), got {dP.shape}")
-        m = dP.shape[1]
-        nw, ng = self._ms_nw, self._ms_ng
-        w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
-                        for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
-        lbw, ubw = _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw")
+        B, point, bounds = self._sens_point(P, res, lbw, ubw, instance_bounds=False)
+        dP = self._sens_cols(dP, B, "dP", of="p")
+        (dw,), flag = self._sens_launches("mpcx_sens_p", B, point, bounds, [dP], (), [(2, (B, self._kdims[0]))])
+        if self._pad is not None:  # the model's own states and inputs only
+            dw = dw[:, self._pad.w_idx]
         nx, nu = self.ocp.nx, self.ocp.nu
-        knx = nx
-        pd = self._pad
-        if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
-            P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
-            dP = pd.scatter(dP.reshape(B * m, -1), pd.p_idx, pd.n_p_pad).reshape(B, m, -1)
-            w, lamx = pd.scatter(w, pd.w_idx, pd.n_w_pad), pd.scatter(lamx, pd.w_idx, pd.n_w_pad)
-            lam = pd.scatter(lam, pd.g_idx, pd.n_g_pad)
-            lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
-            ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
-            nw, knx = pd.n_w_pad, pd.nxp
-        dw = np.empty((B, nw, m))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-        for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
-            mc = min(knx, m - c0)
-            part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
-            dPc = np.ascontiguousarray(dP[:, c0:c0 + mc])
-            _lib.check(lib.mpcx_sens_p(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam), _lib.dptr(lamx),
-                                       _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(dPc), mc, _lib.dptr(part),
-                                       _lib.iptr(fl)))
-            dw[:, :, c0:c0 + mc] = part
-            flag |= fl
-        if pd is not None:  # the model's own states and inputs only
-            dw = dw[:, pd.w_idx]
         du0 = dw[:, nx:nx + nu]
         if self.ocp.formulation == "single_shooting":
-            nz = nx + nu
-            dw = dw[:, np.concatenate([nx + nz * k + np.arange(nu) for k in range(self.ocp.N)])]
+            dw = dw[:, self._ss_rows()]
         return {"dw": np.ascontiguousarray(dw), "du0": np.ascontiguousarray(du0), "flag": flag}
 
     def sens_xref(self, P, res, lbw=None, ubw=None):
@@ -346,52 +296,11 @@ class Solver:
         lbw / ubw: as for :meth:`sens_x0`.
         Returns {'gP': (B, m, n_p), 'flag': (B,)}; flag 1 marks an irregular instance (NaN outputs), as
         :meth:`sens_x0`.  Not for the path-frame bicycle (its stage rows enter the dynamics)."""
-        P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
-        B = P.shape[0]
-        if P.shape[1] != self.n_p:
-            raise ValueError(f"P: expected {self.n_p} columns, got {P.shape[1]}")
-        nw, ng = self._ms_nw, self._ms_ng
-        nx, nu = self.ocp.nx, self.ocp.nu
-        single = self.ocp.formulation == "single_shooting"
-        n_gw = self.ocp.N * nu if single else nw
-        gw = np.asarray(gw, np.float64)
-        if gw.ndim == 2:
-            gw = gw[:, None, :]
-        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != n_gw or gw.shape[1] < 1:
-            raise ValueError(f"gw: expected ({B}, m, {n_gw}) or ({B}, {n_gw}), got {gw.shape}")
-        m = gw.shape[1]
-        if single:  # the control rows of a zero row of w
-            nz = nx + nu
-            full = np.zeros((B, m, nw))
-            full[:, :, np.concatenate([nx + nz * k + np.arange(nu) for k in range(self.ocp.N)])] = gw
-            gw = full
-        w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
-                        for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
-        lbw, ubw = _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw")
-        knx, n_p = nx, self.n_p
-        pd = self._pad
-        if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
-            P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
-            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
-            w, lamx = pd.scatter(w, pd.w_idx, pd.n_w_pad), pd.scatter(lamx, pd.w_idx, pd.n_w_pad)
-            lam = pd.scatter(lam, pd.g_idx, pd.n_g_pad)
-            lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
-            ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
-            knx, n_p = pd.nxp, pd.n_p_pad
-        gP = np.empty((B, m, n_p))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-        for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
-            mc = min(knx, m - c0)
-            part, fl = np.empty((B, mc, n_p)), np.empty(B, np.int32)
-            gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
-            _lib.check(lib.mpcx_sens_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam), _lib.dptr(lamx),
-                                         _lib.dptr(lbw), _lib.dptr(ubw), _lib.dptr(gwc), mc, _lib.dptr(part),
-                                         _lib.iptr(fl)))
-            gP[:, c0:c0 + mc] = part
-            flag |= fl
-        if pd is not None:  # the model's own parameters only
-            gP = gP[:, :, pd.p_idx]
+        B, point, bounds = self._sens_point(P, res, lbw, ubw, instance_bounds=False)
+        gw = self._sens_cols(gw, B, "gw")
+        (gP,), flag = self._sens_launches("mpcx_sens_vjp", B, point, bounds, [gw], (), [(1, (B, self._kdims[2]))])
+        if self._pad is not None:  # the model's own parameters only
+            gP = gP[:, :, self._pad.p_idx]
         return {"gP": np.ascontiguousarray(gP), "flag": flag}
 
     def gain_p(self, P, res, lbw=None, ubw=None):
@@ -407,9 +316,10 @@ class Solver:
         s = self.sens_vjp(P, res, gw, lbw, ubw)
         return {"dU0_dP": s["gP"], "flag": s["flag"]}
 
-    def _sens_bounds_point(self, P, res, lbw, ubw):
-        """What :meth:`sens_bounds` and :meth:`sens_bounds_vjp` share: the point and the bounds in the
-        kernel's layout.  Returns (B, P, w, lam, lamx, lbw, ubw, per_instance)."""
+    def _sens_point(self, P, res, lbw, ubw, instance_bounds=True):
+        """What the sensitivity calls share: the point (P and ``res``: 'w', 'lam_g', 'lam_x') and the
+        bounds in the kernel's layout.  instance_bounds False: bounds shared by the batch only ((B, n_w)
+        arrays are refused).  Returns (B, (P, w, lam, lamx), (lbw, ubw, per_instance))."""
         P = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float64)))
         B = P.shape[0]
         if P.shape[1] != self.n_p:
@@ -417,7 +327,10 @@ class Solver:
         nw, ng = self._ms_nw, self._ms_ng
         w, lam, lamx = (np.ascontiguousarray(np.asarray(res[key], np.float64).reshape(B, n))
                         for key, n in (("w", nw), ("lam_g", ng), ("lam_x", nw)))
-        lbw, ubw, per_instance = _batch_bounds(lbw, ubw, B, nw)
+        if instance_bounds:
+            lbw, ubw, per_instance = _batch_bounds(lbw, ubw, B, nw)
+        else:
+            lbw, ubw, per_instance = _vec(lbw, nw, "lbw"), _vec(ubw, nw, "ubw"), False
         pd = self._pad
         if pd is not None:  # user layout -> the kernel's padded layout (pad states unbounded, 0)
             P = pd.scatter(P, pd.p_idx, pd.n_p_pad)
@@ -428,7 +341,94 @@ class Solver:
             else:
                 lbw = None if lbw is None else pd.scatter(lbw[None, :], pd.w_idx, pd.n_w_pad, -1e20)[0]
                 ubw = None if ubw is None else pd.scatter(ubw[None, :], pd.w_idx, pd.n_w_pad, 1e20)[0]
-        return B, P, w, lam, lamx, lbw, ubw, per_instance
+        return B, (P, w, lam, lamx), (lbw, ubw, per_instance)
+
+    @property
+    def _kdims(self):
+        """(n_w, nx, n_p) of the kernel's layout (the problem's own unless padded)."""
+        pd = self._pad
+        return (self._ms_nw, self.ocp.nx, self.n_p) if pd is None else (pd.n_w_pad, pd.nxp, pd.n_p_pad)
+
+    def _ss_rows(self):
+        """The rows of the multiple-shooting w that are the single-shooting form's w: the controls."""
+        nx, nu = self.ocp.nx, self.ocp.nu
+        return np.concatenate([nx + (nx + nu) * k + np.arange(nu) for k in range(self.ocp.N)])
+
+    def _sens_cols(self, v, B, name, of="w"):
+        """A block of m directions or cotangents, each shaped like a row of w (of the single-shooting
+        form: its control rows) or, with of="p", of P: (B, m, n), or (B, n) for a single one, as
+        (B, m, n) in the kernel's layout."""
+        single = of == "w" and self.ocp.formulation == "single_shooting"
+        n = self.n_p if of == "p" else self.ocp.N * self.ocp.nu if single else self._ms_nw
+        v = np.asarray(v, np.float64)
+        if v.ndim == 2:
+            v = v[:, None, :]
+        if v.ndim != 3 or v.shape[0] != B or v.shape[2] != n or v.shape[1] < 1:
+            raise ValueError(f"{name}: expected ({B}, m, {n}) or ({B}, {n}), got {v.shape}")
+        m = v.shape[1]
+        if single:  # the control rows of a zero row of w
+            full = np.zeros((B, m, self._ms_nw))
+            full[:, :, self._ss_rows()] = v
+            v = full
+        pd = self._pad
+        if pd is not None:
+            idx, n_pad = (pd.p_idx, pd.n_p_pad) if of == "p" else (pd.w_idx, pd.n_w_pad)
+            v = pd.scatter(v.reshape(B * m, -1), idx, n_pad).reshape(B, m, -1)
+        return v
+
+    def _sens_launches(self, entry, B, point, bounds, cols, mid, outs):
+        """The launches of one sensitivity call over m columns, at most nx (of the kernel's layout) of
+        them each: ``entry`` is the host-pointer C entry point (point, bounds, column blocks, *mid, m,
+        outputs, flag), cols the (B, m, .) column blocks and outs a (column axis, shape without it) for
+        every output.  Returns ([the outputs assembled over all m columns], the launches' flags ORed)."""
+        m, knx = cols[0].shape[1], self._kdims[1]
+        entry = getattr(_lib.load(), entry)
+        full = [np.empty(rest[:ax] + (m,) + rest[ax:]) for ax, rest in outs]
+        flag = np.zeros(B, np.int32)
+
+        def call(lb, ub):
+            for c0 in range(0, m, knx):
+                mc = min(knx, m - c0)
+                parts, fl = [np.empty(rest[:ax] + (mc,) + rest[ax:]) for ax, rest in outs], np.empty(B, np.int32)
+                blocks = [np.ascontiguousarray(v[:, c0:c0 + mc]) for v in cols]
+                _lib.check(entry(self._h.ptr, B, *map(_lib.dptr, point), _lib.dptr(lb), _lib.dptr(ub),
+                                 *map(_lib.dptr, blocks), *mid, mc, *map(_lib.dptr, parts), _lib.iptr(fl)))
+                for (ax, _), f, part in zip(outs, full, parts):
+                    f[(slice(None),) * ax + (slice(c0, c0 + mc),)] = part
+                np.bitwise_or(flag, fl, out=flag)
+
+        self._with_bounds(B, *bounds, call)
+        return full, flag
+
+    def _sens_stage_rows(self, entry, B, point, bounds, d):
+        """:meth:`sens_weights` / :meth:`sens_model` once their directions d (B, m, N or 1, .) are rows of
+        the kernel's layout."""
+        (dw,), flag = self._sens_launches(entry, B, point, bounds, [d], (int(d.shape[2] > 1),),
+                                          [(2, (B, self._kdims[0]))])
+        if self._pad is not None:  # the model's own states and inputs only
+            dw = dw[:, self._pad.w_idx]
+        return {"dw": np.ascontiguousarray(dw), "flag": flag}
+
+    def _sens_stage_vjp(self, entry, P, res, gw, lbw, ubw, n_row):
+        """:meth:`sens_weights_vjp` / :meth:`sens_model_vjp` in the kernel's layout (rows of n_row entries):
+        (B, m, the per-stage rows (B, m, N, n_row), their sums over the stages (B, m, n_row), flag)."""
+        B, point, bounds = self._sens_point(P, res, lbw, ubw)
+        gw = self._sens_cols(gw, B, "gw")
+        (gk, gs), flag = self._sens_launches(entry, B, point, bounds, [gw], (),
+                                             [(1, (B, self.ocp.N, n_row)), (1, (B, n_row))])
+        return B, gw.shape[1], gk, gs, flag
+
+    def _sum_by_table(self, B, gk):
+        """Per-stage rows gk (B, m, N, ...) of a linear model summed per table through every instance's
+        schedule: (B, m, n_tab, ...)."""
+        m, N = gk.shape[1], self.ocp.N
+        tab = np.asarray(self.ocp.tab)
+        tab = tab[None, :] if tab.ndim == 1 else tab
+        tab = np.broadcast_to(tab, (B, N)) if tab.shape[0] == 1 else tab[:B]
+        acc = np.zeros((B, m, self.ocp.n_tab) + gk.shape[3:])
+        bi = np.broadcast_to(np.arange(B)[:, None], (B, N))
+        np.add.at(acc, (bi[:, None, :], np.arange(m)[None, :, None], tab[:, None, :]), gk)
+        return acc
 
     def _with_bounds(self, B, lbw, ubw, per_instance, call):
         """Run call(lbw, ubw) with (B, n_w) bounds installed as device bounds for its duration, as
@@ -463,46 +463,17 @@ class Solver:
         with the one-sided multiplier split of include/mpcx.h (mpcx_sens_bounds)."""
         if self.ocp.formulation == "single_shooting":
             raise ValueError("sens_bounds: multiple-shooting layout only (bounds are given on its w)")
-        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
+        B, point, bounds = self._sens_point(P, res, lbw, ubw)
         if dlbw is None and dubw is None:
             raise ValueError("sens_bounds: at least one of dlbw / dubw must be given")
-        nwu = self._ms_nw
-        d = []
-        for v, name in ((dlbw, "dlbw"), (dubw, "dubw")):
-            if v is not None:
-                v = np.asarray(v, np.float64)
-                if v.ndim == 2:
-                    v = v[:, None, :]
-                if v.ndim != 3 or v.shape[0] != B or v.shape[2] != nwu or v.shape[1] < 1:
-                    raise ValueError(f"{name}: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {v.shape}")
-            d.append(v)
+        d = [None if v is None else self._sens_cols(v, B, name) for v, name in ((dlbw, "dlbw"), (dubw, "dubw"))]
         if d[0] is not None and d[1] is not None and d[0].shape != d[1].shape:
-            raise ValueError(f"dlbw {d[0].shape} and dubw {d[1].shape}: the same number of directions expected")
+            sl, su = (v.shape[:2] + (self._ms_nw,) for v in d)  # (as given: the problem's own layout)
+            raise ValueError(f"dlbw {sl} and dubw {su}: the same number of directions expected")
         d = [np.zeros_like(d[1 - i]) if v is None else v for i, v in enumerate(d)]
-        m = d[0].shape[1]
-        nw, knx = nwu, self.ocp.nx
-        pd = self._pad
-        if pd is not None:
-            d = [pd.scatter(v.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1) for v in d]
-            nw, knx = pd.n_w_pad, pd.nxp
-        dw = np.empty((B, nw, m))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-
-        def call(lb, ub):
-            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
-                mc = min(knx, m - c0)
-                part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
-                dl, du = (np.ascontiguousarray(v[:, c0:c0 + mc]) for v in d)
-                _lib.check(lib.mpcx_sens_bounds(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
-                                                _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(dl),
-                                                _lib.dptr(du), mc, _lib.dptr(part), _lib.iptr(fl)))
-                dw[:, :, c0:c0 + mc] = part
-                np.bitwise_or(flag, fl, out=flag)
-
-        self._with_bounds(B, lbw, ubw, per_instance, call)
-        if pd is not None:  # the model's own states and inputs only
-            dw = dw[:, pd.w_idx]
+        (dw,), flag = self._sens_launches("mpcx_sens_bounds", B, point, bounds, d, (), [(2, (B, self._kdims[0]))])
+        if self._pad is not None:  # the model's own states and inputs only
+            dw = dw[:, self._pad.w_idx]
         return {"dw": np.ascontiguousarray(dw), "flag": flag}
 
     def sens_bounds_vjp(self, P, res, gw, lbw=None, ubw=None):
@@ -516,37 +487,13 @@ class Solver:
         there is no finite bound are 0; flag 1 marks an irregular instance (NaN outputs)."""
         if self.ocp.formulation == "single_shooting":
             raise ValueError("sens_bounds_vjp: multiple-shooting layout only (bounds are given on its w)")
-        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
-        nwu = self._ms_nw
-        gw = np.asarray(gw, np.float64)
-        if gw.ndim == 2:
-            gw = gw[:, None, :]
-        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != nwu or gw.shape[1] < 1:
-            raise ValueError(f"gw: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {gw.shape}")
-        m = gw.shape[1]
-        nw, knx = nwu, self.ocp.nx
-        pd = self._pad
-        if pd is not None:
-            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
-            nw, knx = pd.n_w_pad, pd.nxp
-        gl, gu = np.empty((B, m, nw)), np.empty((B, m, nw))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-
-        def call(lb, ub):
-            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
-                mc = min(knx, m - c0)
-                pl, pu, fl = np.empty((B, mc, nw)), np.empty((B, mc, nw)), np.empty(B, np.int32)
-                gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
-                _lib.check(lib.mpcx_sens_bounds_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
-                                                    _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(gwc), mc,
-                                                    _lib.dptr(pl), _lib.dptr(pu), _lib.iptr(fl)))
-                gl[:, c0:c0 + mc], gu[:, c0:c0 + mc] = pl, pu
-                np.bitwise_or(flag, fl, out=flag)
-
-        self._with_bounds(B, lbw, ubw, per_instance, call)
-        if pd is not None:  # the model's own states and inputs only
-            gl, gu = gl[:, :, pd.w_idx], gu[:, :, pd.w_idx]
+        B, point, bounds = self._sens_point(P, res, lbw, ubw)
+        gw = self._sens_cols(gw, B, "gw")
+        nw = self._kdims[0]
+        (gl, gu), flag = self._sens_launches("mpcx_sens_bounds_vjp", B, point, bounds, [gw], (),
+                                             [(1, (B, nw)), (1, (B, nw))])
+        if self._pad is not None:  # the model's own states and inputs only
+            gl, gu = gl[:, :, self._pad.w_idx], gu[:, :, self._pad.w_idx]
         return {"glbw": np.ascontiguousarray(gl), "gubw": np.ascontiguousarray(gu), "flag": flag}
 
     def set_weights(self, Q, R):
@@ -620,32 +567,8 @@ class Solver:
         sensitivities (include/mpcx.h, mpcx_sens_weights)."""
         if self.ocp.formulation == "single_shooting":
             raise ValueError("sens_weights: multiple-shooting layout only")
-        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
-        d = self._weight_rows(B, dQ, dR, dW)
-        m, per_stage = d.shape[1], int(d.shape[2] > 1)
-        nw, knx = self._ms_nw, self.ocp.nx
-        pd = self._pad
-        if pd is not None:
-            nw, knx = pd.n_w_pad, pd.nxp
-        dw = np.empty((B, nw, m))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-
-        def call(lb, ub):
-            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
-                mc = min(knx, m - c0)
-                part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
-                dc = np.ascontiguousarray(d[:, c0:c0 + mc])
-                _lib.check(lib.mpcx_sens_weights(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
-                                                 _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(dc),
-                                                 per_stage, mc, _lib.dptr(part), _lib.iptr(fl)))
-                dw[:, :, c0:c0 + mc] = part
-                np.bitwise_or(flag, fl, out=flag)
-
-        self._with_bounds(B, lbw, ubw, per_instance, call)
-        if pd is not None:  # the model's own states and inputs only
-            dw = dw[:, pd.w_idx]
-        return {"dw": np.ascontiguousarray(dw), "flag": flag}
+        B, point, bounds = self._sens_point(P, res, lbw, ubw)
+        return self._sens_stage_rows("mpcx_sens_weights", B, point, bounds, self._weight_rows(B, dQ, dR, dW))
 
     def sens_weights_vjp(self, P, res, gw, lbw=None, ubw=None):
         """Reverse mode of :meth:`sens_weights` (mpcx_sens_weights_vjp): the gradients with respect to the
@@ -661,49 +584,14 @@ class Solver:
         table through the instance's schedule.  NaN outputs where flag is 1."""
         if self.ocp.formulation == "single_shooting":
             raise ValueError("sens_weights_vjp: multiple-shooting layout only")
-        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
-        nwu = self._ms_nw
-        gw = np.asarray(gw, np.float64)
-        if gw.ndim == 2:
-            gw = gw[:, None, :]
-        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != nwu or gw.shape[1] < 1:
-            raise ValueError(f"gw: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {gw.shape}")
-        m, N = gw.shape[1], self.ocp.N
-        knx = self.ocp.nx
-        pd = self._pad
-        if pd is not None:
-            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
-            knx = pd.nxp
-        n_wt = self._h.weight_dims()
-        gk, gs = np.empty((B, m, N, n_wt)), np.empty((B, m, n_wt))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-
-        def call(lb, ub):
-            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
-                mc = min(knx, m - c0)
-                pk, ps, fl = np.empty((B, mc, N, n_wt)), np.empty((B, mc, n_wt)), np.empty(B, np.int32)
-                gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
-                _lib.check(lib.mpcx_sens_weights_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
-                                                     _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(gwc), mc,
-                                                     _lib.dptr(pk), _lib.dptr(ps), _lib.iptr(fl)))
-                gk[:, c0:c0 + mc], gs[:, c0:c0 + mc] = pk, ps
-                np.bitwise_or(flag, fl, out=flag)
-
-        self._with_bounds(B, lbw, ubw, per_instance, call)
+        B, m, gk, gs, flag = self._sens_stage_vjp("mpcx_sens_weights_vjp", P, res, gw, lbw, ubw, self._h.weight_dims())
         if self.ocp.model != "linear":
             nx = self.ocp.nx
             return {"gQ": np.ascontiguousarray(gs[..., :nx]), "gR": np.ascontiguousarray(gs[..., nx:]),
                     "gQk": np.ascontiguousarray(gk[..., :nx]), "gRk": np.ascontiguousarray(gk[..., nx:]), "flag": flag}
         sel, _ = self._wt_sel()
         gk = np.ascontiguousarray(gk[..., sel])
-        tab = np.asarray(self.ocp.tab)
-        tab = tab[None, :] if tab.ndim == 1 else tab
-        tab = np.broadcast_to(tab, (B, N)) if tab.shape[0] == 1 else tab[:B]
-        gW = np.zeros((B, m, self.ocp.n_tab, sel.size))
-        bi = np.broadcast_to(np.arange(B)[:, None], (B, N))
-        np.add.at(gW, (bi[:, None, :], np.arange(m)[None, :, None], tab[:, None, :]), gk)
-        return {"gWk": gk, "gW": gW, "flag": flag}
+        return {"gWk": gk, "gW": self._sum_by_table(B, gk), "flag": flag}
 
     def set_par(self, par):
         """Replace the constants ``par`` of an ODE model (mpcx_set_par; not for linear models, whose constants
@@ -785,32 +673,8 @@ class Solver:
             raise ValueError("sens_model: multiple-shooting layout only")
         if self.ocp.model == "unicycle":
             raise ValueError("sens_model: the unicycle has no model constants")
-        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
-        d = self._model_rows(B, dpar, dA, dB, dc)
-        m, per_stage = d.shape[1], int(d.shape[2] > 1)
-        nw, knx = self._ms_nw, self.ocp.nx
-        pd = self._pad
-        if pd is not None:
-            nw, knx = pd.n_w_pad, pd.nxp
-        dw = np.empty((B, nw, m))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-
-        def call(lb, ub):
-            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) columns per launch
-                mc = min(knx, m - c0)
-                part, fl = np.empty((B, nw, mc)), np.empty(B, np.int32)
-                dc_ = np.ascontiguousarray(d[:, c0:c0 + mc])
-                _lib.check(lib.mpcx_sens_model(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
-                                               _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(dc_),
-                                               per_stage, mc, _lib.dptr(part), _lib.iptr(fl)))
-                dw[:, :, c0:c0 + mc] = part
-                np.bitwise_or(flag, fl, out=flag)
-
-        self._with_bounds(B, lbw, ubw, per_instance, call)
-        if pd is not None:  # the model's own states and inputs only
-            dw = dw[:, pd.w_idx]
-        return {"dw": np.ascontiguousarray(dw), "flag": flag}
+        B, point, bounds = self._sens_point(P, res, lbw, ubw)
+        return self._sens_stage_rows("mpcx_sens_model", B, point, bounds, self._model_rows(B, dpar, dA, dB, dc))
 
     def sens_model_vjp(self, P, res, gw, lbw=None, ubw=None):
         """Reverse mode of :meth:`sens_model` (mpcx_sens_model_vjp): the gradients with respect to the model
@@ -828,49 +692,17 @@ class Solver:
             raise ValueError("sens_model_vjp: multiple-shooting layout only")
         if self.ocp.model == "unicycle":
             raise ValueError("sens_model_vjp: the unicycle has no model constants")
-        B, P, w, lam, lamx, lbw, ubw, per_instance = self._sens_bounds_point(P, res, lbw, ubw)
-        nwu = self._ms_nw
-        gw = np.asarray(gw, np.float64)
-        if gw.ndim == 2:
-            gw = gw[:, None, :]
-        if gw.ndim != 3 or gw.shape[0] != B or gw.shape[2] != nwu or gw.shape[1] < 1:
-            raise ValueError(f"gw: expected ({B}, m, {nwu}) or ({B}, {nwu}), got {gw.shape}")
-        m, N = gw.shape[1], self.ocp.N
-        pd = self._pad
-        if pd is not None:
-            gw = pd.scatter(gw.reshape(B * m, -1), pd.w_idx, pd.n_w_pad).reshape(B, m, -1)
         knx, nu, n_th = self._model_dims()
-        gk, gs = np.empty((B, m, N, n_th)), np.empty((B, m, n_th))
-        flag = np.zeros(B, np.int32)
-        lib = _lib.load()
-
-        def call(lb, ub):
-            for c0 in range(0, m, knx):  # at most nx (of the kernel's layout) cotangents per launch
-                mc = min(knx, m - c0)
-                pk, ps, fl = np.empty((B, mc, N, n_th)), np.empty((B, mc, n_th)), np.empty(B, np.int32)
-                gwc = np.ascontiguousarray(gw[:, c0:c0 + mc])
-                _lib.check(lib.mpcx_sens_model_vjp(self._h.ptr, B, _lib.dptr(P), _lib.dptr(w), _lib.dptr(lam),
-                                                   _lib.dptr(lamx), _lib.dptr(lb), _lib.dptr(ub), _lib.dptr(gwc), mc,
-                                                   _lib.dptr(pk), _lib.dptr(ps), _lib.iptr(fl)))
-                gk[:, c0:c0 + mc], gs[:, c0:c0 + mc] = pk, ps
-                np.bitwise_or(flag, fl, out=flag)
-
-        self._with_bounds(B, lbw, ubw, per_instance, call)
+        B, m, gk, gs, flag = self._sens_stage_vjp("mpcx_sens_model_vjp", P, res, gw, lbw, ubw, n_th)
         if self.ocp.model != "linear":
             return {"gpar": gs, "gpark": gk, "flag": flag}
-        nx = self.ocp.nx
+        nx, N = self.ocp.nx, self.ocp.N
         gAk = np.ascontiguousarray(gk[..., :knx * knx].reshape(B, m, N, knx, knx)[..., :nx, :nx])
         gBk = np.ascontiguousarray(gk[..., knx * knx:knx * knx + knx * nu].reshape(B, m, N, knx, nu)[..., :nx, :])
         gck = np.ascontiguousarray(gk[..., knx * knx + knx * nu:][..., :nx])
-        tab = np.asarray(self.ocp.tab)
-        tab = tab[None, :] if tab.ndim == 1 else tab
-        tab = np.broadcast_to(tab, (B, N)) if tab.shape[0] == 1 else tab[:B]
-        bi = np.broadcast_to(np.arange(B)[:, None], (B, N))
         out = {"gAk": gAk, "gBk": gBk, "gck": gck, "flag": flag}
         for name, v in (("gA", gAk), ("gB", gBk), ("gc", gck)):  # summed over the schedule, as gW is
-            acc = np.zeros((B, m, self.ocp.n_tab) + v.shape[3:])
-            np.add.at(acc, (bi[:, None, :], np.arange(m)[None, :, None], tab[:, None, :]), v)
-            out[name] = acc
+            out[name] = self._sum_by_table(B, v)
         return out
 
     def rk4_sens(self, w, P):

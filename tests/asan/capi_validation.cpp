@@ -92,6 +92,31 @@ int main() {
   char kname[256];
   EXPECT(mpcx_launch_shape(nullptr, 16, &lanes, &reps, kname, (int32_t)sizeof(kname)) < 0);
   mpcx_destroy(nullptr);
+  int32_t n_row;
+  EXPECT(mpcx_weight_dims(nullptr, &n_row) < 0);
+  EXPECT(mpcx_model_dims(nullptr, &n_row) < 0);
+  EXPECT(mpcx_set_weights(nullptr, d, d) < 0);
+  EXPECT(mpcx_set_par(nullptr, d) < 0);
+  // the sensitivity calls, host-pointer and device-pointer: the null handle is refused first, by name
+  auto null_handle = [](int r) { return r < 0 && std::strcmp(mpcx_last_error(), "null handle") == 0; };
+  EXPECT(null_handle(mpcx_sens_x0(nullptr, 1, d, d, d, d, nullptr, nullptr, d, d, i32)));
+  EXPECT(null_handle(mpcx_sens_x0_dev(nullptr, 1, d, d, d, d, d, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_p(nullptr, 1, d, d, d, d, nullptr, nullptr, d, 1, d, i32)));
+  EXPECT(null_handle(mpcx_sens_p_dev(nullptr, 1, d, d, d, d, d, 1, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_vjp(nullptr, 1, d, d, d, d, nullptr, nullptr, d, 1, d, i32)));
+  EXPECT(null_handle(mpcx_sens_vjp_dev(nullptr, 1, d, d, d, d, d, 1, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_bounds(nullptr, 1, d, d, d, d, nullptr, nullptr, d, d, 1, d, i32)));
+  EXPECT(null_handle(mpcx_sens_bounds_dev(nullptr, 1, d, d, d, d, d, d, 1, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_bounds_vjp(nullptr, 1, d, d, d, d, nullptr, nullptr, d, 1, d, d, i32)));
+  EXPECT(null_handle(mpcx_sens_bounds_vjp_dev(nullptr, 1, d, d, d, d, d, 1, d, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_weights(nullptr, 1, d, d, d, d, nullptr, nullptr, d, 0, 1, d, i32)));
+  EXPECT(null_handle(mpcx_sens_weights_dev(nullptr, 1, d, d, d, d, d, 0, 1, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_weights_vjp(nullptr, 1, d, d, d, d, nullptr, nullptr, d, 1, d, d, i32)));
+  EXPECT(null_handle(mpcx_sens_weights_vjp_dev(nullptr, 1, d, d, d, d, d, 1, d, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_model(nullptr, 1, d, d, d, d, nullptr, nullptr, d, 0, 1, d, i32)));
+  EXPECT(null_handle(mpcx_sens_model_dev(nullptr, 1, d, d, d, d, d, 0, 1, d, i32, nullptr)));
+  EXPECT(null_handle(mpcx_sens_model_vjp(nullptr, 1, d, d, d, d, nullptr, nullptr, d, 1, d, d, i32)));
+  EXPECT(null_handle(mpcx_sens_model_vjp_dev(nullptr, 1, d, d, d, d, d, 1, d, d, i32, nullptr)));
 
   // a valid spec: created where a device exists, refused with a HIP error elsewhere
   mpcx_default_spec(&s, MPCX_MODEL_UNICYCLE, 20);
