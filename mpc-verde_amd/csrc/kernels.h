@@ -1634,7 +1634,13 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
           soft_tried = !go;
           DIAG(12);
         }
-        if (__any(go)) {
+        // Only the groups that take the step run it (exec-masked, group-uniform; block-uniform for
+        // multi-wave groups): eval_at overwrites the lane's derivative arrays, and a wave neighbour
+        // that has just accepted its line search's first trial keeps that trial's evaluation for
+        // its next iteration -- run by the whole wave, the step left such a neighbour the
+        // derivatives at z + min(alpha_max, alpha_z) dz instead, so its bits depended on its wave
+        // mates (tests/test_gpu_resto_exits.py test_lanes_do_not_leak).
+        if (go) {
           if (!sw_set) switching();  // (a soft phase skips the filter search)
           const double as = fmin(amax, az);
           double zt[NZ], lt[NX];
@@ -1701,7 +1707,7 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
           }
           fresh = false;  // the arrays hold the trial point's evaluation (kept if it is accepted)
           const bool infilter = filt.contains(tht, pht, xw);
-          if (go) {
+          {
             // the original criteria first ...
             bool acc = isfinite(pht) && isfinite(tht) && tht <= theta_max;
             bool ft = false;
