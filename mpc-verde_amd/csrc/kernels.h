@@ -257,6 +257,7 @@ struct RowChainOf<M, std::void_t<decltype(M::kRowChain)>> {
 
 }  // namespace mpcx
 #include "backward.h"  // the backward Riccati sweeps, one function per strategy
+#include "forward.h"   // the forward sweep, the bound-dual step and the step lengths
 namespace mpcx {
 
 // R = 2 (replicated groups, G = 32): a batch too small to give every SIMD a wave runs one
@@ -1269,206 +1270,34 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
     STAMP(4);
     phase();
     // ------------------------------------------------------------ forward sweep: dw (lane k-1 -> k)
-    // (a lambda: the second-order correction re-runs it with other right-hand sides)
-    auto forward = [&](const double* cc_, const double* kf_, const double* pv_, const double* c0v_, double* dzo_,
-                       double* dlo_) __attribute__((always_inline)) {
-      // closed-loop map of the step, node-parallel (off the sequential chain):
-      // dx_{k+1} = (A + B K) dx_k + (c + B k_f);  du_k = k_f + K dx_k afterwards
-      double Acl[NX * NX], ccl[NX];
-      double Aw_[kWsStash ? NX * NX : 1], Bw_[kWsStash ? NX * NU : 1];
-      const double* Af_ = Model::jacA(ctx, A);
-      const double* Bf_ = Model::jacB(ctx, Bm);
+    // (csrc/forward.h; the second-order correction re-runs it with other right-hand sides)
+    // the Jacobians of the step: the model's, or this lane's copy back from the workspace (kWsStash)
+    auto step_jac = [&](double* Aw_, double* Bw_, const double*& Af_, const double*& Bf_) __attribute__((always_inline)) {
+      Af_ = Model::jacA(ctx, A);
+      Bf_ = Model::jacB(ctx, Bm);
       if constexpr (kWsStash) {
         ws_jac(Aw_, Bw_);
         Af_ = Aw_;
         Bf_ = Bw_;
       }
-#pragma unroll
-      for (int r = 0; r < NX; ++r) {
-        double acc = cc_[r];
-#pragma unroll
-        for (int l = 0; l < NU; ++l)
-          if (Model::BMASK & (1ull << (r * NU + l))) acc = fma(Bf_[r * NU + l], kf_[l], acc);
-        ccl[r] = acc;
-#pragma unroll
-        for (int m = 0; m < NX; ++m) {
-          double e = (Model::AMASK & (1ull << (r * NX + m))) ? Af_[r * NX + m] : 0.0;
-#pragma unroll
-          for (int l = 0; l < NU; ++l)
-            if (Model::BMASK & (1ull << (r * NU + l))) e = fma(Bf_[r * NU + l], Kk[l * NX + m], e);
-          Acl[r * NX + m] = e;
-        }
-      }
-      {
-        // dx_k = T_{k-1}( ... T_0(c0)) with affine T_j(x) = Acl_j x + ccl_j: an inclusive
-        // parallel prefix of map compositions (log2 GW levels per wave, all lanes busy) instead
-        // of N+1 dependent steps.  Lane k starts with T_{k-1} (lane 0: the constant map c0) and
-        // composes with the partial map of its DPP partner at each level: Kogge-Stone inside
-        // each 16-lane row, then the previous rows' totals by row broadcasts (scan_partner; the
-        // ds_bpermute version of the same scan, Hillis-Steele over lane k-d: config 2 16.3 us per
-        // IPM iteration against 15.8 us with the DPP partners, config 3 35.0 against 33.7 us).
-        // Multi-wave groups scan every wave at once; the first lane of wave w gets
-        // T_{64w-1} from wave w-1 through LDS, and the waves' partial results are chained
-        // by one LDS handoff of dx per wave boundary.
-        constexpr int NM = NX * NX + NX;
-        constexpr int GW = G < 64 ? G : 64;  // lanes scanned per wave
-        const int wv = G > 64 ? (int)(threadIdx.x >> 6) : 0;
-        double Am[NX * NX], cm[NX];
-        {
-          double own[NM], prv[NM];
-#pragma unroll
-          for (int i = 0; i < NX * NX; ++i) own[i] = Acl[i];
-#pragma unroll
-          for (int i = 0; i < NX; ++i) own[NX * NX + i] = ccl[i];
-#pragma unroll
-          for (int i = 0; i < NM; ++i) prv[i] = from_prev(own[i]);
-          if constexpr (G > 64) {  // lane 0 of wave w > 0: T_{64w-1} lives on lane 63 of wave w-1
-            double* b = xw.cur();
-            if (lane == 63 && wv < XWave<G>::W - 1)
-#pragma unroll
-              for (int i = 0; i < NM; ++i) b[wv * kXchStride + i] = own[i];
-            xw.sync();
-            if (lane == 0 && wv > 0)
-#pragma unroll
-              for (int i = 0; i < NM; ++i) prv[i] = xw.prev()[(wv - 1) * kXchStride + i];
-          }
-          // lane 1 takes only T_0's constant part: dx_1 = B_0 du_0 + c_1 does not depend on dx_0
-          // (interval 0 integrates from x0, A_0 = 0)
-#pragma unroll
-          for (int i = 0; i < NX * NX; ++i) Am[i] = (k <= 1) ? 0.0 : prv[i];
-#pragma unroll
-          for (int i = 0; i < NX; ++i) cm[i] = (k == 0) ? c0v_[i] : prv[NX * NX + i];
-        }
-        const int kw = k & (GW - 1);  // position inside the wave
-        // one level: compose with the partial map of the DPP partner (collectives.h scan_partner)
-        auto level = [&](auto dc) __attribute__((always_inline)) {
-          constexpr int d = decltype(dc)::value;
-          if constexpr (d < GW) {
-          double Ao[NX * NX], co[NX];
-#pragma unroll
-          for (int i = 0; i < NX * NX; ++i) Ao[i] = scan_partner<d>(Am[i]);
-#pragma unroll
-          for (int i = 0; i < NX; ++i) co[i] = scan_partner<d>(cm[i]);
-          if (scan_takes<d>(kw)) {  // compose: (Am, cm) o (Ao, co)
-            double An[NX * NX], cn[NX];
-#pragma unroll
-            for (int r = 0; r < NX; ++r) {
-              double acc = cm[r];
-#pragma unroll
-              for (int m = 0; m < NX; ++m) acc = fma(Am[r * NX + m], co[m], acc);
-              cn[r] = acc;
-#pragma unroll
-              for (int c = 0; c < NX; ++c) {
-                double e = Am[r * NX] * Ao[c];
-#pragma unroll
-                for (int m = 1; m < NX; ++m) e = fma(Am[r * NX + m], Ao[m * NX + c], e);
-                An[r * NX + c] = e;
-              }
-            }
-#pragma unroll
-            for (int i = 0; i < NX * NX; ++i) Am[i] = An[i];
-#pragma unroll
-            for (int i = 0; i < NX; ++i) cm[i] = cn[i];
-          }
-          }
-        };
-        level(std::integral_constant<int, 1>{});
-        level(std::integral_constant<int, 2>{});
-        level(std::integral_constant<int, 4>{});
-        level(std::integral_constant<int, 8>{});
-        level(std::integral_constant<int, 16>{});
-        level(std::integral_constant<int, 32>{});
-        if constexpr (G > 64) {
-          // wave w's lanes hold maps dx_{64w-1} -> dx_k; chain the waves in order
-          for (int ph = 1; ph < XWave<G>::W; ++ph) {
-            double* b = xw.cur();
-            if (wv == ph - 1 && lane == 63)
-#pragma unroll
-              for (int i = 0; i < NX; ++i) b[i] = cm[i];
-            xw.sync();
-            if (wv == ph) {
-              const double* in = xw.prev();
-              double cn[NX];
-#pragma unroll
-              for (int r = 0; r < NX; ++r) {
-                double acc = cm[r];
-#pragma unroll
-                for (int m = 0; m < NX; ++m) acc = fma(Am[r * NX + m], in[m], acc);
-                cn[r] = acc;
-              }
-#pragma unroll
-              for (int i = 0; i < NX; ++i) cm[i] = cn[i];
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < NX; ++i) dzo_[i] = cm[i];
-      }
-      // du_k = k_f + K dx_k on all lanes at once (the last node has no control)
-#pragma unroll
-      for (int l = 0; l < NU; ++l) {
-        double acc = kf_[l];
-#pragma unroll
-        for (int m = 0; m < NX; ++m) acc = fma(Kk[l * NX + m], dzo_[m], acc);
-        dzo_[NX + l] = (k < N) ? acc : 0.0;
-      }
-      // lambda+ = P_k dx_k + p_k (node-parallel, after the sequential sweep)
-#pragma unroll
-      for (int i = 0; i < NX; ++i) {
-        double acc = pv_[i];
-#pragma unroll
-        for (int m = 0; m < NX; ++m) acc = fma(Pk[symix(i, m, NX)], dzo_[m], acc);
-        dlo_[i] = acc - lam[i];
-      }
-      if (!hasX) {
-#pragma unroll
-        for (int i = 0; i < NZ; ++i) dzo_[i] = 0.0;
-#pragma unroll
-        for (int i = 0; i < NX; ++i) dlo_[i] = 0.0;
-      }
     };
-    forward(cdef, kfk, pk, c0, dz, dlam);
+    {
+      double Aw_[kWsStash ? NX * NX : 1], Bw_[kWsStash ? NX * NU : 1];
+      const double *Af_, *Bf_;
+      step_jac(Aw_, Bw_, Af_, Bf_);
+      forward_sweep<Model, G>(k, N, hasX, Af_, Bf_, Kk, Pk, lam, cdef, kfk, pk, c0, xw, dz, dlam);
+    }
 
     STAMP(5);
     phase();
     // ------------------------------------------------------------ bound-dual step, fraction to boundary
-    double amax_l = 1.0, az_l = 1.0, tiny_l = -1.0, gd_l = 0.0;
-#pragma unroll
-    for (int i = 0; i < NZ; ++i) {
-      dzL[i] = dzU[i] = 0.0;
-      const double rdz = rcp64(dz[i]);
-      if (hL[i]) {
-        const double s = z[i] - lb[i], rs = rcp64(s);
-        dzL[i] = fma(mu, rs, -zL[i]) - zL[i] * rs * dz[i];
-        if (dz[i] < 0) amax_l = fmin(amax_l, -tau * s * rdz);
-        if (dzL[i] < 0) az_l = fmin(az_l, -tau * zL[i] * rcp64(dzL[i]));
-      }
-      if (hU[i]) {
-        const double s = ub[i] - z[i], rs = rcp64(s);
-        dzU[i] = fma(mu, rs, -zU[i]) + zU[i] * rs * dz[i];
-        if (dz[i] > 0) amax_l = fmin(amax_l, tau * s * rdz);
-        if (dzU[i] < 0) az_l = fmin(az_l, -tau * zU[i] * rcp64(dzU[i]));
-      }
-      const bool own = (i < NX) ? hasX : hasU;
-      // IPOPT's tiny step test max |dz_i| / (1 + |z_i|) < 10 eps as the sign of
-      // |dz_i| - 10 eps (1 + |z_i|) (one fma, no reciprocal)
-      tiny_l = qmax(tiny_l, own ? fma(-10.0 * kEps, 1.0 + fabs(z[i]), fabs(dz[i])) : -1.0);
-      if (own) gd_l += gp[i] * dz[i];
-    }
-    // amax, az (min), gd (sum) and the tiny-step test (max over the group < 0) in one exchange
-    double fr[4] = {amax_l, az_l, gd_l, tiny_l < 0.0 ? 1.0 : 0.0};
-    if constexpr (G > 64) {
-      greduce_n<G, 2, 2, 0, 3>(fr, xw);
-    } else {
-      greduce_n<G, 2, 2, 0>(fr, xw);
-      fr[3] = gall<G, G * R>(tiny_l < 0.0, xw) ? 1.0 : 0.0;
-    }
-    const double amax = fr[0];
-    double az = fr[1];  // dual step length (a second-order correction replaces it)
-    const bool tinystep = fr[3] > 0.5;
+    double amax_l, az_l;
+    bound_step<NZ>(z, dz, lb, ub, hL, hU, zL, zU, mu, tau, dzL, dzU, amax_l, az_l);
+    double amax, az, gd;  // az: dual step length (a second-order correction replaces it)
+    bool tinystep;
+    step_lengths<G, R, NX, NU>(hasX, hasU, z, dz, gp, amax_l, az_l, xw, amax, az, gd, tinystep);
     if (!done && amax < 1.0) DIAG(4);
     if (!done && tinystep) DIAG(5);
-    const double gd = fr[2];
 
     STAMP(6);
     phase();
@@ -1929,26 +1758,15 @@ __global__ __launch_bounds__(G * R > 64 ? G * R : 64) void solve_kernel(SolveArg
 #pragma unroll
               for (int i = 0; i < NX; ++i) pv[i] = gp[i];
             double dzs[NZ], dls[NX];
-            forward(cs, kfs, pv, cs0, dzs, dls);
-            // primal and dual fraction to the boundary along the correction
-            double am_l = 1.0, azs_l = 1.0, dzLs[NZ], dzUs[NZ];
-#pragma unroll
-            for (int i = 0; i < NZ; ++i) {
-              dzLs[i] = dzUs[i] = 0.0;
-              const double rdz = rcp64(dzs[i]);
-              if (hL[i]) {
-                const double sl = z[i] - lb[i], rs = rcp64(sl);
-                dzLs[i] = fma(mu, rs, -zL[i]) - zL[i] * rs * dzs[i];
-                if (dzs[i] < 0) am_l = fmin(am_l, -tau * sl * rdz);
-                if (dzLs[i] < 0) azs_l = fmin(azs_l, -tau * zL[i] * rcp64(dzLs[i]));
-              }
-              if (hU[i]) {
-                const double su = ub[i] - z[i], rs = rcp64(su);
-                dzUs[i] = fma(mu, rs, -zU[i]) + zU[i] * rs * dzs[i];
-                if (dzs[i] > 0) am_l = fmin(am_l, tau * su * rdz);
-                if (dzUs[i] < 0) azs_l = fmin(azs_l, -tau * zU[i] * rcp64(dzUs[i]));
-              }
+            {
+              double Aw_[kWsStash ? NX * NX : 1], Bw_[kWsStash ? NX * NU : 1];
+              const double *Af_, *Bf_;
+              step_jac(Aw_, Bw_, Af_, Bf_);
+              forward_sweep<Model, G>(k, N, hasX, Af_, Bf_, Kk, Pk, lam, cs, kfs, pv, cs0, xw, dzs, dls);
             }
+            // primal and dual fraction to the boundary along the correction
+            double am_l, azs_l, dzLs[NZ], dzUs[NZ];
+            bound_step<NZ>(z, dzs, lb, ub, hL, hU, zL, zU, mu, tau, dzLs, dzUs, am_l, azs_l);
             const double as = gmin<G>(am_l, xw), azs = gmin<G>(azs_l, xw);
             double zs[NZ];
 #pragma unroll
